@@ -133,7 +133,12 @@ def setup():
                          "and more; never = the interpreter kernel (A/B)")
     ap.add_argument("--expr-limbs", type=int, default=0, choices=[0, 32],
                     help="halo2 work-list, quotient expression: 0 = lazy 29-bit limbs over cosets written in the R' radix (default); 32 = the saturated evaluator (A/B)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, see dump_outputs()) "
+                         "to compare two builds output for output; the inputs are seeded, so the same arguments give the same inputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -175,6 +180,40 @@ def setup():
 
 def to_dev(e, arr):
     return e.torch.from_numpy(e.np.ascontiguousarray(arr).view(e.np.int64)).cuda()
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_ROWS = 1 << 16
+
+
+def sample_rows(e, d, seed):
+    """a fixed, seeded sample of the rows of a device vector [n, limbs] (all of them when n <= DUMP_SAMPLE_ROWS) -> host uint64"""
+    host = d.cpu().numpy().view(e.np.uint64)
+    if host.shape[0] <= DUMP_SAMPLE_ROWS:
+        return host
+    return host[e.np.sort(e.np.random.default_rng(seed).choice(host.shape[0], DUMP_SAMPLE_ROWS, replace=False))]
+
+
+def affine(e, curve, pts):
+    """Jacobian points [..., 3 * limbs] -> affine [..., 2 * limbs] (one representation per point, whatever the order of additions)"""
+    pts = e.np.asarray(pts, dtype=e.np.uint64)
+    return e.np.stack([e.zk.point_to_affine(curve, p) for p in pts.reshape(-1, pts.shape[-1])]).reshape(pts.shape[:-1] + (-1,))
+
+
+def dump_outputs(e, outputs):
+    """--dump-outputs DIR: {name: uint64 limb array} -> DIR/<name>.npy.  Field elements are written as the library returns them
+    (Montgomery limbs), points in affine form.  Every 64-bit limb becomes four float32 values, its 16-bit pieces from the least
+    significant one: exact, and a change in any bit of a limb moves one value by at least 2^-16 of its size."""
+    np = e.np
+    arrs = {}
+    for name, a in outputs.items():
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        arrs[name] = a.view(np.uint16).reshape(a.shape[:-1] + (4 * a.shape[-1],)).astype(np.float32)
+    total = sum(a.nbytes for a in arrs.values())
+    assert total <= DUMP_MAX_BYTES, "outputs of %d bytes exceed the %d-byte dump budget" % (total, DUMP_MAX_BYTES)
+    os.makedirs(e.args.dump_outputs, exist_ok=True)
+    for name, a in arrs.items():
+        np.save(os.path.join(e.args.dump_outputs, name + ".npy"), a)
 
 
 def make_bases(e, curve, n, seed):
@@ -469,7 +508,7 @@ def bench_halo2(e):
             result["prof"] = zk.msm_last_profile()
         t1 = time.perf_counter()
         # ---- 2 lookup: the permuted columns
-        commit_batch(g_lagrange, d_lookup[2:4])
+        result["lookup_commitments"] = commit_batch(g_lagrange, d_lookup[2:4])
         t2 = time.perf_counter()
         # ---- 3 permutation: chunk c + 1 continues from the last value of chunk c; columns = 13 advice + 3 instance
         z_first = None
@@ -492,7 +531,7 @@ def bench_halo2(e):
         t_rand = None
         if e.world == 1 and not a.serial:
             t_rand = zk.msm_submit(g_coeff, d_coef[row[("random", 0)]], montgomery=True, window_bits=a.window_bits, stream=e.st, own_stream=True)
-        commit_batch(g_lagrange, d_z)
+        result["product_commitments"] = commit_batch(g_lagrange, d_z)
         t3 = time.perf_counter()
         t4 = t3
         # ---- 5 vanishing argument's random polynomial, 6 quotient
@@ -588,7 +627,7 @@ def bench_halo2(e):
                 H.kate_division(sfield, dst, pt, stream=e.st)
             if s_:
                 H.vec_muladd(sfield, d_qprime, d_tmp, x2, stream=e.st)
-        commit(g_coeff, d_qprime)
+        result["q_commitment"] = commit(g_coeff, d_qprime)
         result["q_evals"] = H.eval_polynomials(sfield, d_q, x3, stream=e.st)
         for s_ in range(len(sets)):                             # p = q' x_4^4 + ... : one Horner step per set
             H.vec_muladd(sfield, d_qprime, d_q[s_], x4, stream=e.st)
@@ -610,8 +649,9 @@ def bench_halo2(e):
             ipa = H.IpaProverVirtual(curve, d_ipa[0], d_ipa[1], g_coeff, lambda shape: torch.zeros(shape, dtype=torch.int64, device="cuda"),
                                      stream=e.st, buffers=(d_S, d_W))
         small = False
+        result["ipa_rounds"] = []
         for j in range(k):
-            ipa.round(sharded=e.world > 1)
+            result["ipa_rounds"].append(ipa.round(sharded=e.world > 1))
             ipa.fold(us[j])
             if a.ipa == "collapse" and (j + 1) in collapse_at and j + 1 < k:
                 ipa.collapse(sharded=e.world > 1)
@@ -628,6 +668,16 @@ def bench_halo2(e):
                 phase_ms[name] += dt * 1e3
 
     elapsed = timed(e, step)
+    if a.dump_outputs is not None and e.rank == 0:
+        pt = lambda v: affine(e, curve, v)
+        ipa_l, ipa_r, ipa_vl, ipa_vr = (np.stack(v) for v in zip(*result["ipa_rounds"]))
+        dump_outputs(e, {"instance_advice_commitments": pt(result["commitments"]), "lookup_permuted_commitments": pt(result["lookup_commitments"]),
+                         "product_commitments": pt(result["product_commitments"]), "random_commitment": pt(result["random_commitment"]),
+                         "h_commitments": pt(result["h_commitments"]), "evals_at_x": result["evals"][0], "evals_at_omega_x": result["evals"][1],
+                         "evals_at_omega_inv_x": result["evals"][2], "evals_at_omega_last_x": result["evals"][3],
+                         "q_commitment": pt(result["q_commitment"]), "q_evals_at_x3": result["q_evals"], "s_commitment": pt(result["s_commitment"]),
+                         "v": result["v"], "ipa_L": pt(ipa_l), "ipa_R": pt(ipa_r), "ipa_vl": ipa_vl, "ipa_vr": ipa_vr,
+                         "ipa_a": d_ipa[0][:1].cpu().numpy().view(np.uint64)})
     # the library totals were drained class by class inside the steps: rebuild the whole-run sums for rooflines()
     tot = dict.fromkeys(e.msm_tot, 0)
     for cs in cls_sum.values():
@@ -807,6 +857,8 @@ def bench_column(e):
         main.wait_stream(side)
 
     elapsed = timed(e, step)
+    if a.dump_outputs is not None and e.rank == 0:     # the NTT runs in place: d_a holds the last step's transform
+        dump_outputs(e, {"msm": affine(e, curve, result["msm"]), "ntt_sample": sample_rows(e, d_a, 0xD0A)})
     if e.rank == 0:
         prof = zk.msm_last_profile()
         m = e.msm_tot
@@ -896,6 +948,11 @@ def bench_groth16(e):
             phases["witness_map_ms"] += evs[0].elapsed_time(evs[1])
 
     elapsed = timed(e, step)
+    if a.dump_outputs is not None and e.rank == 0:     # h: the witness map's output of the last step (in place in d_abc[0])
+        out = {name: affine(e, c, p) for name, c, p in zip(("b_g2_query_msm", "h_query_msm", "a_query_msm", "b_g1_query_msm", "l_query_msm"),
+                                                            (g2, g1, g1, g1, g1), result["pts"])}
+        out["witness_map_h_sample"] = sample_rows(e, d_abc[0], 0xD0B)
+        dump_outputs(e, out)
     if e.rank == 0:
         mt = e.msm_tot
         line = base_line(e, m * a.steps / elapsed, elapsed,

@@ -1,6 +1,6 @@
 """GPU tier (-m gpu): the HIP library on a real MI355X, through the C ABI, against the CPU oracle
 and the pure-Python golden fixtures.  Bit-exact bar (integer arithmetic).  Nothing here reads
-/root/reference.  Full-size (2^20) cases use size-independent properties plus the oracle's
+the reference project.  Full-size (2^20) cases use size-independent properties plus the oracle's
 threaded restatement where it finishes in seconds."""
 import os
 
@@ -719,20 +719,26 @@ def test_ntt_lazy_limbs_extremes(zk):
                 assert (got == orc.halo2_best_fft(name, a, w, logn, threads=16)).all(), (name, logn, pattern)
 
 
-def test_bench_work_lists_run(zk):
+def test_bench_work_lists_run(zk, tmp_path):
     """bench.py's three work-lists at a small size, one step each, as subprocesses: the JSON line carries the contract's keys
-    (the full-size numbers come from the driver's own run)"""
+    (the full-size numbers come from the driver's own run), and --dump-outputs writes the step's outputs as float32 arrays"""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    for extra in (["--logn", "12"], ["--logn", "12", "--serial"], ["--workload", "column", "--logn", "14"],
-                  ["--workload", "groth16", "--curve", "Bls381G1", "--logn", "12"]):
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--no-cpu-baseline"] + extra,
-                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    for i, extra in enumerate((["--logn", "12"], ["--logn", "12", "--serial"], ["--workload", "column", "--logn", "14"],
+                               ["--workload", "groth16", "--curve", "Bls381G1", "--logn", "12"])):
+        dump = tmp_path / str(i)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
+                            "--dump-outputs", str(dump)] + extra, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
         line = json.loads(r.stdout.strip().splitlines()[-1])
         for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
                     "data", "config", "roofline"):
             assert key in line, (extra, key)
         assert line["value"] > 0 and "workload" in line["config"] and line["roofline"]["frac"] > 0
+        names = os.listdir(dump)
+        assert len(names) >= 2 and all(n.endswith(".npy") for n in names), (extra, names)
+        for n in names:
+            out = np.load(dump / n)
+            assert out.dtype == np.float32 and out.size and out.any(), (extra, n)
