@@ -700,6 +700,17 @@ ExprJitKernel* expr_jit_get(DeviceCtx& dc, const std::string& src) {
 }
 #endif
 
+// the specialised kernel's column slots and waves per SIMD (its __launch_bounds__): ZK_EXPR_JIT_SLOTS (1 .. 8) and
+// ZK_EXPR_JIT_WAVES (1 .. 8) (tuning), read the same way by the evaluator and by zk_expr_specialised_source
+inline uint32_t expr_jit_slots() {
+    const char* e = getenv("ZK_EXPR_JIT_SLOTS");
+    return e && atoi(e) >= 1 && atoi(e) <= (int)EXPR_JIT_SLOTS_MAX ? (uint32_t)atoi(e) : EXPR_JIT_SLOTS;
+}
+inline int expr_jit_waves() {
+    const char* e = getenv("ZK_EXPR_JIT_WAVES");
+    return e && atoi(e) >= 1 && atoi(e) <= 8 ? atoi(e) : 2;
+}
+
 // the source of the specialised kernel for a program, without a device (zk_expr_specialised_source: diagnostics, the CPU test tier)
 template <class F>
 int expr_source_run(const zk_expr_op* prog, uint32_t n_ops, uint32_t n_cols, uint32_t n_consts, std::string& out) {
@@ -708,8 +719,9 @@ int expr_source_run(const zk_expr_op* prog, uint32_t n_ops, uint32_t n_cols, uin
     std::vector<const void*> cols(n_cols ? n_cols : 1, (const void*)&out);      // (the walk only asks that a column be present)
     std::vector<uint64_t> words;
     uint32_t depth = 0;
-    ZK_TRY(expr_compile29<F>(prog, n_ops, n_cols, cols.data(), n_consts, words, depth, EXPR_JIT_SLOTS));
-    out = expr_jit_source<F>(words, EXPR_JIT_SLOTS, 2);
+    const uint32_t nslots = expr_jit_slots();
+    ZK_TRY(expr_compile29<F>(prog, n_ops, n_cols, cols.data(), n_consts, words, depth, nslots));
+    out = expr_jit_source<F>(words, nslots, expr_jit_waves());
     return out.empty() ? ZK_ERR_INVALID_ARG : ZK_OK;
 #else
     (void)prog, (void)n_ops, (void)n_cols, (void)n_consts, (void)out;
@@ -730,9 +742,7 @@ int expr_eval_lazy_run(DeviceCtx& dc, const zk_expr_op* prog, uint32_t n_ops, co
 #if !defined(ZK_EMU) && defined(ZK_FIELD)
     want_jit = g.expr_jit == 1 || (g.expr_jit == 0 && log_n >= 16);
 #endif
-    uint32_t nslots = want_jit ? EXPR_JIT_SLOTS : EXPR29_SLOTS;
-    if (want_jit)
-        if (const char* e = getenv("ZK_EXPR_JIT_SLOTS")) nslots = atoi(e) >= 1 && atoi(e) <= (int)EXPR_JIT_SLOTS_MAX ? (uint32_t)atoi(e) : nslots;   // (tuning)
+    const uint32_t nslots = want_jit ? expr_jit_slots() : EXPR29_SLOTS;
     ZK_TRY(expr_compile29<F>(prog, n_ops, n_cols, cols, n_consts, words, depth, nslots));
     if (getenv("ZK_EXPR_STATS")) {     // (diagnostic) the executed program by opcode: what the bound walk added to the caller's ops
         uint32_t cnt[16] = {0};
@@ -758,8 +768,7 @@ int expr_eval_lazy_run(DeviceCtx& dc, const zk_expr_op* prog, uint32_t n_ops, co
     const uint64_t n = 1ull << log_n;
 #if !defined(ZK_EMU) && defined(ZK_FIELD)
     if (want_jit) {
-        int waves = 2;
-        if (const char* e = getenv("ZK_EXPR_JIT_WAVES")) waves = atoi(e) >= 1 && atoi(e) <= 8 ? atoi(e) : 2;
+        const int waves = expr_jit_waves();
         const std::string src = expr_jit_source<F>(words, nslots, waves);
         ExprJitKernel* jk = src.empty() ? nullptr : expr_jit_get<F>(dc, src);
         if (jk) {

@@ -14,7 +14,7 @@ import ctypes
 
 import numpy as np
 
-from . import (Bases, _check, _np64, _ptr, base_limbs, curve_id, field_id, field_inverse, field_modulus, load, msm, msm_batch, msm_submit,
+from . import (Bases, ZkError, _check, _np64, _ptr, base_limbs, curve_id, field_id, field_inverse, field_modulus, load, msm, msm_batch, msm_submit,
                multiplicative_generator, ntt, root_of_unity, scalar_field, vec_op)
 
 PROVER_EXPORTS = ["zk_batch_invert_device", "zk_prefix_product_device", "zk_halo2_permutation_product_device",
@@ -261,6 +261,7 @@ class ExprOp(ctypes.Structure):
     _fields_ = [("op", ctypes.c_uint8), ("pad", ctypes.c_uint8), ("rot", ctypes.c_int16), ("arg", ctypes.c_uint32)]
 
 
+ZK_ERR_INVALID_ARG = -1        # include/zkcp_amd.h
 EXPR_CODES = {"col": 0, "const": 1, "add": 2, "sub": 3, "mul": 4, "neg": 5, "scale": 6}
 
 
@@ -467,15 +468,26 @@ def ipa_fold_bases(curve, g, half, u, stream=0):
     return g
 
 
+def _expr_ops(program):
+    """the program as zk_expr_op records.  ctypes truncates an out-of-range integer without an error (a rotation of 40000 would
+    become -25536 in the int16 field), so every field is range-checked here first: a program that cannot be written as it is
+    stated is refused, never evaluated as a different one"""
+    ops = (ExprOp * len(program))()
+    for k, o in enumerate(program):
+        if not isinstance(o, (tuple, list)) or not o or o[0] not in EXPR_CODES or len(o) != {"col": 3, "const": 2, "scale": 2}.get(o[0], 1):
+            raise ZkError(ZK_ERR_INVALID_ARG, "expression op %d %r" % (k, o))
+        arg, rot = (int(o[1]) if len(o) > 1 else 0), (int(o[2]) if len(o) > 2 else 0)
+        if not 0 <= arg < 1 << 32 or not -(1 << 15) <= rot < 1 << 15:
+            raise ZkError(ZK_ERR_INVALID_ARG, "expression op %d %r: index or rotation out of range" % (k, o))
+        ops[k].op, ops[k].rot, ops[k].arg = EXPR_CODES[o[0]], rot, arg
+    return ops
+
+
 def evaluate_expression(field, program, columns, consts, log_n_ext, rot_scale, out, stream=0, lazy=False):
     """program: list of ("col", column, rotation) / ("const", i) / ("add",) / ("sub",) / ("mul",) / ("neg",) / ("scale", i).
     lazy: the columns hold x R' mod p (coeff_to_extended(..., lazy_out=True) / to_lazy_form) and the evaluation runs on lazy
     29-bit limbs; constants and the output stay in the usual Montgomery form"""
-    ops = (ExprOp * len(program))()
-    for k, o in enumerate(program):
-        ops[k].op = EXPR_CODES[o[0]]
-        ops[k].rot = o[2] if o[0] == "col" else 0
-        ops[k].arg = o[1] if len(o) > 1 else 0
+    ops = _expr_ops(program)
     cs = _np64(consts).reshape(-1, 4) if len(consts) else np.zeros((1, 4), dtype=np.uint64)
     fn = _plib().zk_expr_eval_lazy_device if lazy else _plib().zk_expr_eval_device
     _check(fn(field_id(field), ops, len(program), _ptr_array(columns), len(columns), _ptr(cs), len(consts), log_n_ext,
@@ -490,11 +502,7 @@ def expr_configure(jit="auto"):
 
 def expr_specialised_source(field, program, n_columns, n_consts):
     """the HIP source of the kernel zk_expr_eval_lazy_device compiles for `program` (no device needed)"""
-    ops = (ExprOp * len(program))()
-    for i, o in enumerate(program):
-        ops[i].op = EXPR_CODES[o[0]]
-        ops[i].rot = int(o[2]) if o[0] == "col" and len(o) > 2 else 0
-        ops[i].arg = int(o[1]) if len(o) > 1 else 0
+    ops = _expr_ops(program)
     n = ctypes.c_uint64(0)
     fid = field_id(field)
     _check(_plib().zk_expr_specialised_source(fid, ops, len(program), n_columns, n_consts, None, 0, ctypes.byref(n)), "zk_expr_specialised_source")
