@@ -152,6 +152,9 @@ void free_device(DeviceCtx& dc) {
         ws_free(s->poly_a);
         ws_free(s->poly_b);
         ws_free(s->poly_tot);
+        ws_free(s->lk_keys);
+        ws_free(s->lk_runs);
+        ws_free(s->lk_meta);
         if (s->pinned) hipHostFree(s->pinned);
         if (s->pinned_ev) hipEventDestroy(s->pinned_ev);
         s->pinned = nullptr;
@@ -496,6 +499,7 @@ API const char* zk_strerror(int s) {
         case ZK_ERR_UNSUPPORTED: return "unsupported size or curve";
         case ZK_ERR_BAD_HANDLE: return "unknown bases handle or MSM ticket";
         case ZK_ERR_BUSY: return "too many MSMs in flight on this device: collect one first";
+        case ZK_ERR_LOOKUP: return "a lookup input value is not in the table";
         default: return "unknown status";
     }
 }
@@ -1347,6 +1351,33 @@ API int zk_halo2_lookup_product_device(zk_field_t f, const void* a, const void* 
         fe_one(one);
         return lookup_product_run<F>(dc, (const Fe<F>*)a, (const Fe<F>*)s, (const Fe<F>*)ap, (const Fe<F>*)sp, b, g_, n, one, (Fe<F>*)z_out,
                                      z_last_host, (hipStream_t)stream);
+    });
+    return ZK_ERR_INVALID_ARG;
+}
+// [p, p + bytes) and [q, q + bytes) share an address
+static bool ranges_overlap(const void* p, const void* q, uint64_t bytes) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + bytes && b < a + bytes;
+}
+API int zk_halo2_permute_expression_pair_device(zk_field_t f, const void* inputs_dev, const void* table_dev, uint64_t usable_rows, void* a_perm_dev,
+                                                void* s_perm_dev, void* stream) {
+    if (usable_rows >= (1ull << 31)) return ZK_ERR_INVALID_ARG;
+    if (usable_rows) {
+        const void* ptrs[4] = {inputs_dev, table_dev, a_perm_dev, s_perm_dev};
+        for (const void* p : ptrs)
+            if (!p || !aligned16(p)) return ZK_ERR_INVALID_ARG;
+        const uint64_t bytes = usable_rows * 32;
+        if (ranges_overlap(a_perm_dev, s_perm_dev, bytes) || ranges_overlap(a_perm_dev, inputs_dev, bytes) ||
+            ranges_overlap(a_perm_dev, table_dev, bytes) || ranges_overlap(s_perm_dev, inputs_dev, bytes) ||
+            ranges_overlap(s_perm_dev, table_dev, bytes))
+            return ZK_ERR_INVALID_ARG;
+    }
+    DEVICE_ENTRY(a_perm_dev);
+    FIELD_SWITCH(f, {
+        int failed = 0;
+        ZK_TRY(permute_expression_pair_run<F>(dc, (const Fe<F>*)inputs_dev, (const Fe<F>*)table_dev, (uint32_t)usable_rows, (Fe<F>*)a_perm_dev,
+                                              (Fe<F>*)s_perm_dev, &failed, (hipStream_t)stream));
+        return failed ? ZK_ERR_LOOKUP : ZK_OK;
     });
     return ZK_ERR_INVALID_ARG;
 }

@@ -127,6 +127,7 @@ struct StreamScratch {
     uint64_t stamp = 0;
     DevBuf ntt_tmp, fb_table, fb_tmp;
     DevBuf poly_a, poly_b, poly_tot;   // numerators / denominators / block totals of the grand-product and IPA helpers
+    DevBuf lk_keys, lk_runs, lk_meta;  // permute_expression_pair: key ping-pong pair, pass counts + run arrays, histogram + meta words
     void* pinned = nullptr;            // small pinned host buffer: results that are read back without stalling the stream at once
     size_t pinned_cap = 0;
     hipEvent_t pinned_ev = nullptr;    // recorded after the copies into `pinned`

@@ -34,6 +34,11 @@ int perm_product_run(DeviceCtx& dc, int field, uint32_t ncols, const void* const
 template <class F>
 int lookup_product_run(DeviceCtx& dc, const Fe<F>* A, const Fe<F>* S, const Fe<F>* Ap, const Fe<F>* Sp, const Fe<F>& beta, const Fe<F>& gamma,
                        uint64_t n, const Fe<F>& first, Fe<F>* z_out, void* total_host, hipStream_t st);
+// plonk/lookup/prover.rs permute_expression_pair (zk_lookup.inl): A', S' of the first u rows; *lookup_failed = 1 when an input
+// value is not in the table (synchronises the stream once, at the end)
+template <class F>
+int permute_expression_pair_run(DeviceCtx& dc, const Fe<F>* A, const Fe<F>* S, uint32_t u, Fe<F>* a_out, Fe<F>* s_out, int* lookup_failed,
+                                hipStream_t st);
 template <class F>
 int inner_product_run(DeviceCtx& dc, const Fe<F>* a, const Fe<F>* b, uint64_t n, void* out_host, hipStream_t st);
 template <class F>

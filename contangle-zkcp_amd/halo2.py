@@ -18,7 +18,7 @@ from . import (Bases, ZkError, _check, _np64, _ptr, base_limbs, curve_id, field_
                multiplicative_generator, ntt, root_of_unity, scalar_field, vec_op)
 
 PROVER_EXPORTS = ["zk_batch_invert_device", "zk_prefix_product_device", "zk_halo2_permutation_product_device",
-                  "zk_halo2_lookup_product_device", "zk_inner_product_device", "zk_vec_fold_device", "zk_ipa_fold_bases_device",
+                  "zk_halo2_lookup_product_device", "zk_halo2_permute_expression_pair_device", "zk_inner_product_device", "zk_vec_fold_device", "zk_ipa_fold_bases_device",
                   "zk_expr_eval_device", "zk_ipa_virtual_scalars_device", "zk_ipa_update_weights_device", "zk_ipa_collapse_device", "zk_ipa_collapse_range_device", "zk_ipa_round_device",
                   "zk_poly_eval_device", "zk_poly_eval_batch_device", "zk_vec_muladd_device", "zk_vec_muladd_to_device", "zk_kate_division_device", "zk_vec_powers_device", "zk_vec_fold_many_device",
                   "zk_ipa_fold_round_device", "zk_expr_eval_lazy_device", "zk_expr_configure", "zk_expr_specialised_source"]
@@ -273,6 +273,7 @@ def _plib():
     lib.zk_prefix_product_device.argtypes = [i32, vp, vp, u64, vp, vp, vp]
     lib.zk_halo2_permutation_product_device.argtypes = [i32, u32, pp, pp, u32, vp, vp, vp, u32, vp, vp, vp, vp]
     lib.zk_halo2_lookup_product_device.argtypes = [i32, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]
+    lib.zk_halo2_permute_expression_pair_device.argtypes = [i32, vp, vp, u64, vp, vp, vp]
     lib.zk_inner_product_device.argtypes = [i32, vp, vp, u64, vp, vp]
     lib.zk_vec_fold_device.argtypes = [i32, vp, u64, vp, vp]
     lib.zk_ipa_fold_bases_device.argtypes = [i32, vp, u64, vp, vp]
@@ -342,6 +343,29 @@ def permute_expression_pair(field, inputs_mont, table_mont, usable_rows):
     assert len(leftovers) == len(repeated)
     s_perm[repeated[::-1]] = leftovers                              # upstream pops the repeated rows from the last one down
     return to_mont(a), to_mont(s_perm)
+
+
+ZK_ERR_LOOKUP = -9
+
+
+def permute_expression_pair_device(field, inputs, table, usable_rows, a_out=None, s_out=None, stream=0):
+    """permute_expression_pair on device buffers (zk_halo2_permute_expression_pair_device): rows [0, usable_rows) of the
+    Montgomery columns `inputs` and `table` in, (A', S') out -- rows [0, usable_rows) written, later rows left alone.  Outputs
+    of usable_rows rows are allocated beside the inputs when none are given.  Raises ValueError where upstream returns
+    ConstraintSystemFailure, like the host routine above."""
+    def alloc():
+        if isinstance(inputs, np.ndarray):
+            return np.zeros((usable_rows, 4), dtype=np.uint64)
+        import torch
+        return torch.empty((usable_rows, 4), dtype=torch.int64, device=inputs.device)
+    a_out = alloc() if a_out is None else a_out
+    s_out = alloc() if s_out is None else s_out
+    st = _plib().zk_halo2_permute_expression_pair_device(field_id(field), _ptr(inputs), _ptr(table), int(usable_rows), _ptr(a_out), _ptr(s_out),
+                                                          ctypes.c_void_p(stream))
+    if st == ZK_ERR_LOOKUP:
+        raise ValueError("ConstraintSystemFailure: a lookup input is not in the table")
+    _check(st, "zk_halo2_permute_expression_pair_device")
+    return a_out, s_out
 
 
 def batch_invert(field, a, stream=0):

@@ -69,7 +69,8 @@ typedef enum {
     ZK_ERR_OOM = -5,
     ZK_ERR_UNSUPPORTED = -6,
     ZK_ERR_BAD_HANDLE = -7,
-    ZK_ERR_BUSY = -8          /* 4 MSMs are already in flight on the device: collect one first */
+    ZK_ERR_BUSY = -8,         /* 4 MSMs are already in flight on the device: collect one first */
+    ZK_ERR_LOOKUP = -9        /* a lookup input value is not in the table (halo2 Error::ConstraintSystemFailure) */
 } zk_status;
 
 /* MSM tuning / sharding.  Zero-initialise for defaults. */

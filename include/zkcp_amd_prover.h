@@ -121,9 +121,22 @@ int zk_halo2_permutation_product_device(zk_field_t f, uint32_t ncols, const void
                                         uint32_t first_column_index, const void *beta, const void *gamma, const void *delta, uint32_t k,
                                         const void *z_first, void *z_out_dev, void *z_last_out_host, void *hip_stream);
 /* plonk/lookup/prover.rs commit_product: Z(0) = 1, Z(i + 1) = Z(i) (A_i + beta)(S_i + gamma) / ((A'_i + beta)(S'_i + gamma));
- * A', S' are the permuted input / table expressions (permute_expression_pair: a sort, left to the caller) */
+ * A', S' are the permuted input / table expressions (zk_halo2_permute_expression_pair_device below) */
 int zk_halo2_lookup_product_device(zk_field_t f, const void *a_dev, const void *s_dev, const void *a_perm_dev, const void *s_perm_dev,
                                    const void *beta, const void *gamma, uint64_t n, void *z_out_dev, void *z_last_out_host, void *hip_stream);
+/* plonk/lookup/prover.rs permute_expression_pair, the deterministic part: the compressed input expression A and table
+ * expression S (Montgomery, n x 4 u64, 16-B aligned) -> the permuted pair A', S'.  Reads rows [0, usable_rows) of each input
+ * and writes exactly rows [0, usable_rows) of each output; rows from usable_rows on are left to the caller's blinding rows.
+ * The inputs are not modified.
+ *   A'  the inputs sorted by the field's Ord (canonical integers, not Montgomery limbs);
+ *   S'  at the first row of every run of equal values in A' that value; the leftover table values, ascending, fill the
+ *       repeated-input rows from the last one up (upstream's repeated_input_rows.pop()).
+ * An input value that is not in the table returns ZK_ERR_LOOKUP (upstream: Error::ConstraintSystemFailure); A', S' are then
+ * unspecified and the library stays usable.  All work is enqueued on hip_stream; the call synchronises it once, at the end,
+ * to read the status word.  ZK_ERR_INVALID_ARG: null or misaligned pointers, outputs that overlap each other or either
+ * input, usable_rows >= 2^31.  usable_rows = 0 does nothing.  Scratch: about 160 B per usable row, owned by the stream. */
+int zk_halo2_permute_expression_pair_device(zk_field_t f, const void *inputs_dev, const void *table_dev, uint64_t usable_rows,
+                                            void *a_perm_dev, void *s_perm_dev, void *hip_stream);
 /* poly/commitment/prover.rs create_proof, the scalar side of one round: compute_inner_product, and the folds
  * p'[i] += u^-1 p'[i + half], b[i] += u b[i + half] as a[i] += c a[i + half] */
 int zk_inner_product_device(zk_field_t f, const void *a_dev, const void *b_dev, uint64_t n, void *out_mont_host, void *hip_stream);

@@ -22,6 +22,7 @@ pub const ZK_PAIRING_BN254: c_int = 0;
 pub const ZK_PAIRING_BLS12_381: c_int = 1;
 pub const ZK_OK: c_int = 0;
 pub const ZK_ERR_BUSY: c_int = -8;
+pub const ZK_ERR_LOOKUP: c_int = -9;
 
 #[repr(C)]
 #[derive(Default, Clone, Copy)]
@@ -233,6 +234,8 @@ extern "C" {
     pub fn zk_halo2_lookup_product_device(f: c_int, a_dev: *const c_void, s_dev: *const c_void, a_perm_dev: *const c_void,
                                           s_perm_dev: *const c_void, beta: *const c_void, gamma: *const c_void, n: u64, z_out_dev: *mut c_void,
                                           z_last_out_host: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn zk_halo2_permute_expression_pair_device(f: c_int, inputs_dev: *const c_void, table_dev: *const c_void, usable_rows: u64,
+                                                   a_perm_dev: *mut c_void, s_perm_dev: *mut c_void, hip_stream: *mut c_void) -> c_int;
     pub fn zk_inner_product_device(f: c_int, a_dev: *const c_void, b_dev: *const c_void, n: u64, out_mont_host: *mut c_void,
                                    hip_stream: *mut c_void) -> c_int;
     pub fn zk_poly_eval_device(f: c_int, coeffs_dev: *const c_void, n: u64, x_mont_host: *const c_void, out_mont_host: *mut c_void,
