@@ -3,6 +3,7 @@
   VariableBaseMSM.multi_scalar_mul(bases, scalars)   ark-ec 0.3  src/msm/variable_base.rs
   Radix2EvaluationDomain(num_coeffs)                 ark-poly 0.3 src/domain/radix2/mod.rs
       .fft_in_place / .ifft_in_place / .coset_fft_in_place / .coset_ifft_in_place
+      .evaluate_all_lagrange_coefficients(tau)       (key generation: ark-groth16 0.3 generate_parameters)
   FixedBaseMSM.multi_scalar_mul(...)                 ark-ec 0.3  src/msm/fixed_base.rs  (key generation,
                                                      lib/src/zk/encryption.rs:169 via ark-groth16 0.3 generate_parameters)
 
@@ -69,6 +70,13 @@ class Radix2EvaluationDomain:
     def _check(self, a):
         if int(a.shape[0]) != self.size:
             raise ValueError("ark-poly resizes to the domain size; pass exactly %d coefficients" % self.size)
+
+    def evaluate_all_lagrange_coefficients(self, tau, d_out, stream=0):
+        """d_out[i] = L_i(tau) for a tau outside the domain (Montgomery limbs; device buffer of `size` elements) -- the first step of
+        ark-groth16 0.3 generate_parameters; returns evaluate_vanishing_polynomial(tau) = tau^size - 1"""
+        from . import groth16
+        self._check(d_out)
+        return groth16.lagrange_coefficients(self.field, self.log_size_of_group, tau, d_out, stream=stream)
 
     def fft_in_place(self, a):
         self._check(a)

@@ -361,3 +361,4 @@ int witness_map_run(DeviceCtx& dc, int field, Fe<F>* a, Fe<F>* b, Fe<F>* c, uint
 }  // namespace zk
 #include "zk_poly.inl"
 #include "zk_lookup.inl"
+#include "zk_setup.inl"

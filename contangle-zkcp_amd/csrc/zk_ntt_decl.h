@@ -12,6 +12,11 @@ struct R1csMatrix {
     int field = 0;
     uint64_t n_rows = 0, n_cols = 0, nnz = 0, n_long = 0;
     void *row_ptr = nullptr, *col = nullptr, *val = nullptr, *long_rows = nullptr;
+    // the column-major companion (zk_setup_kernels.h): built on the device at the first transposed product, freed with the handle.
+    // col_ptr: n_cols + 1 u32 offsets; t_row / t_val: row index and coefficient per term; long_cols: columns over R1CS_LONG_ROW terms
+    bool t_ready = false;
+    uint64_t n_long_cols = 0;
+    void *col_ptr = nullptr, *t_row = nullptr, *t_val = nullptr, *long_cols = nullptr;
 };
 template <class F>
 int ntt_run(DeviceCtx& dc, int field, Fe<F>* a, uint32_t logn, const Fe<F>& omega, int scale_flag, hipStream_t st,
@@ -73,6 +78,23 @@ int expr_eval_lazy_run(DeviceCtx& dc, const zk_expr_op* prog, uint32_t n_ops, co
                        uint32_t n_consts, uint32_t log_n, uint32_t rot_scale, Fe<F>* out, hipStream_t st);
 template <class F>
 int r1cs_matvec_run(const R1csMatrix& m, const Fe<F>* z, Fe<F>* out, uint64_t out_len, hipStream_t st);
+// Groth16 key generation (zk_setup.inl)
+template <class F>
+int r1cs_transpose_run(R1csMatrix& m, hipStream_t st);
+template <class F>
+int r1cs_matvec_t_run(const R1csMatrix& m, const Fe<F>* x, uint64_t x_len, Fe<F>* out, uint64_t out_len, const Fe<F>* extra, uint64_t n_extra,
+                      hipStream_t st);
+template <class F>
+int lagrange_consts(uint32_t logm, const Fe<F>& tau, Fe<F>* w_out, Fe<F>* zt_out, Fe<F>* s_out);
+template <class F>
+int lagrange_run(DeviceCtx& dc, int field, uint32_t logm, const Fe<F>& tau, Fe<F>* out, Fe<F>* zt_out, hipStream_t st);
+template <class F>
+int groth16_qap_at_run(DeviceCtx& dc, int field, const R1csMatrix& ma, const R1csMatrix& mb, const R1csMatrix& mc, uint64_t num_inputs,
+                       uint32_t logm, const Fe<F>& tau, Fe<F>* u, Fe<F>* v, Fe<F>* w, uint64_t n_vars, Fe<F>* zt_out, hipStream_t st);
+template <class F>
+int groth16_key_scalars_run(DeviceCtx& dc, const Fe<F>* u, const Fe<F>* v, const Fe<F>* w, uint64_t n_vars, uint64_t num_inputs, uint32_t logm,
+                            const Fe<F>& alpha, const Fe<F>& beta, const Fe<F>& gamma, const Fe<F>& delta, const Fe<F>& tau, const Fe<F>& zt,
+                            Fe<F>* abc, Fe<F>* h, hipStream_t st);
 template <class F>
 int witness_map_run(DeviceCtx& dc, int field, Fe<F>* a, Fe<F>* b, Fe<F>* c, uint32_t logm, hipStream_t st);
 }  // namespace zk

@@ -32,4 +32,13 @@ template int expr_eval_lazy_run<ZK_FIELD>(DeviceCtx&, const zk_expr_op*, uint32_
 template int expr_source_run<ZK_FIELD>(const zk_expr_op*, uint32_t, uint32_t, uint32_t, std::string&);
 template int r1cs_matvec_run<ZK_FIELD>(const R1csMatrix&, const Fe<ZK_FIELD>*, Fe<ZK_FIELD>*, uint64_t, hipStream_t);
 template int witness_map_run<ZK_FIELD>(DeviceCtx&, int, Fe<ZK_FIELD>*, Fe<ZK_FIELD>*, Fe<ZK_FIELD>*, uint32_t, hipStream_t);
+template int r1cs_transpose_run<ZK_FIELD>(R1csMatrix&, hipStream_t);
+template int r1cs_matvec_t_run<ZK_FIELD>(const R1csMatrix&, const Fe<ZK_FIELD>*, uint64_t, Fe<ZK_FIELD>*, uint64_t, const Fe<ZK_FIELD>*, uint64_t, hipStream_t);
+template int lagrange_consts<ZK_FIELD>(uint32_t, const Fe<ZK_FIELD>&, Fe<ZK_FIELD>*, Fe<ZK_FIELD>*, Fe<ZK_FIELD>*);
+template int lagrange_run<ZK_FIELD>(DeviceCtx&, int, uint32_t, const Fe<ZK_FIELD>&, Fe<ZK_FIELD>*, Fe<ZK_FIELD>*, hipStream_t);
+template int groth16_qap_at_run<ZK_FIELD>(DeviceCtx&, int, const R1csMatrix&, const R1csMatrix&, const R1csMatrix&, uint64_t, uint32_t, const Fe<ZK_FIELD>&,
+                                          Fe<ZK_FIELD>*, Fe<ZK_FIELD>*, Fe<ZK_FIELD>*, uint64_t, Fe<ZK_FIELD>*, hipStream_t);
+template int groth16_key_scalars_run<ZK_FIELD>(DeviceCtx&, const Fe<ZK_FIELD>*, const Fe<ZK_FIELD>*, const Fe<ZK_FIELD>*, uint64_t, uint64_t, uint32_t,
+                                               const Fe<ZK_FIELD>&, const Fe<ZK_FIELD>&, const Fe<ZK_FIELD>&, const Fe<ZK_FIELD>&, const Fe<ZK_FIELD>&,
+                                               const Fe<ZK_FIELD>&, Fe<ZK_FIELD>*, Fe<ZK_FIELD>*, hipStream_t);
 }  // namespace zk

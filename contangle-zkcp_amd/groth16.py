@@ -5,18 +5,26 @@ lib/src/zk/encryption.rs:76, verifiable_encryption.rs:92, sample_entries.rs:86, 
   witness_map                r1cs_to_qap.rs R1CStoQAP::witness_map from the full assignment: 3 sparse mat-vecs + 7 NTTs + glue
   Prover.prove(z, r, s)      prover.rs create_proof_with_reduction_and_matrices: witness map -> h ; the five MSMs
                              (submitted back to back, collected afterwards) ; assembly of A, B, C ; ark_to_bytes(proof)
+  generate_parameters        generator.rs generate_parameters (what the reference's `compile` runs through Groth16::setup,
+                             lib/src/zk/encryption.rs:169): Lagrange coefficients at tau, the QAP at tau from the resident
+                             matrices (three TRANSPOSED sparse mat-vecs), the key scalars, the fixed-base multiplications;
+                             -> Parameters: point vectors on the device, serialize_unchecked() = the key file `compile` writes
+  generate_random_parameters the same with the five trapdoor scalars drawn from `secrets`
 
 The blinding scalars r, s are arguments: upstream draws them from the caller's RNG, so a proof is reproducible bit for
 bit only when the unmodified Rust prover drives the FFI (SURVEY 7 "hard parts"); everything before them is deterministic.
 """
 import ctypes
+import secrets
 
 import numpy as np
 
-from . import (_check, _np64, _ptr, ark_serialize, base_limbs, field_id, load, msm_submit, vec_op)
+from . import (Bases, _check, _np64, _ptr, ark_serialize, backend_info, base_limbs, field_id, field_modulus, fixed_base_msm_device, load,
+               msm_submit, vec_op)
 
 PROVER_EXPORTS = ["zk_r1cs_matrix_upload", "zk_r1cs_matrix_free", "zk_r1cs_matvec_device", "zk_groth16_witness_map_r1cs_device",
-                  "zk_groth16_assemble_proof"]
+                  "zk_groth16_assemble_proof", "zk_r1cs_matvec_transposed_device", "zk_lagrange_coefficients_device",
+                  "zk_groth16_qap_at_device", "zk_groth16_key_scalars_device"]
 
 
 class Assembly(ctypes.Structure):
@@ -32,6 +40,10 @@ def _lib():
     lib.zk_r1cs_matvec_device.argtypes = [u64, vp, vp, u64, vp]
     lib.zk_groth16_witness_map_r1cs_device.argtypes = [i32, u64, u64, u64, vp, u64, ctypes.c_uint32, vp, vp, vp, vp]
     lib.zk_groth16_assemble_proof.argtypes = [i32, ctypes.POINTER(Assembly), vp, vp, vp]
+    lib.zk_r1cs_matvec_transposed_device.argtypes = [u64, vp, u64, vp, u64, vp]
+    lib.zk_lagrange_coefficients_device.argtypes = [i32, ctypes.c_uint32, vp, vp, vp, vp]
+    lib.zk_groth16_qap_at_device.argtypes = [i32, u64, u64, u64, u64, ctypes.c_uint32, vp, vp, vp, vp, u64, vp, vp]
+    lib.zk_groth16_key_scalars_device.argtypes = [i32, vp, vp, vp, u64, u64, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     return lib
 
 
@@ -65,6 +77,14 @@ class R1csMatrix:
     def matvec(self, d_z, d_out, stream=0):
         _check(_lib().zk_r1cs_matvec_device(self.handle, _ptr(d_z), _ptr(d_out), int(d_out.shape[0]), ctypes.c_void_p(stream)),
                "zk_r1cs_matvec_device")
+        return d_out
+
+    def matvec_transposed(self, d_x, d_out, x_len=None, stream=0):
+        """d_out[j] = sum_i M[i][j] d_x[i] over the rows i < x_len (default: all of d_x); d_out[n_cols:] = 0.  The first call on a
+        matrix builds its column-major companion on the device."""
+        x_len = int(d_x.shape[0]) if x_len is None else int(x_len)
+        _check(_lib().zk_r1cs_matvec_transposed_device(self.handle, _ptr(d_x), x_len, _ptr(d_out), int(d_out.shape[0]), ctypes.c_void_p(stream)),
+               "zk_r1cs_matvec_transposed_device")
         return d_out
 
     def free(self):
@@ -144,3 +164,153 @@ class Prover:
             b.free()
         for mtx in (self.A, self.B, self.C):
             mtx.free()
+
+
+# ---- key generation: ark-groth16 0.3 generator.rs generate_parameters ----
+def lagrange_coefficients(field, log_m, tau, d_out, stream=0):
+    """d_out[i] = L_i(tau) on the size-2^log_m domain (evaluate_all_lagrange_coefficients); returns zt = tau^m - 1 (Montgomery limbs)"""
+    zt = np.zeros(4, dtype=np.uint64)
+    _check(_lib().zk_lagrange_coefficients_device(field_id(field), int(log_m), _ptr(_np64(tau)), _ptr(d_out), _ptr(zt), ctypes.c_void_p(stream)),
+           "zk_lagrange_coefficients_device")
+    return zt
+
+
+def qap_at(field, A, B, C, num_inputs, log_m, tau, d_u, d_v, d_w, stream=0):
+    """LibsnarkReduction::instance_map_with_evaluation: the QAP polynomials u, v, w of every variable at tau (device buffers of
+    n_vars elements); returns zt"""
+    zt = np.zeros(4, dtype=np.uint64)
+    n_vars = int(d_u.shape[0])
+    assert int(d_v.shape[0]) == n_vars and int(d_w.shape[0]) == n_vars
+    _check(_lib().zk_groth16_qap_at_device(field_id(field), A.handle, B.handle, C.handle, int(num_inputs), int(log_m), _ptr(_np64(tau)),
+                                           _ptr(d_u), _ptr(d_v), _ptr(d_w), n_vars, _ptr(zt), ctypes.c_void_p(stream)),
+           "zk_groth16_qap_at_device")
+    return zt
+
+
+def key_scalars(field, d_u, d_v, d_w, num_inputs, log_m, alpha, beta, gamma, delta, tau, zt, d_abc, d_h, stream=0):
+    """d_abc = (beta u + alpha v + w) / gamma for the inputs, / delta for the rest; d_h[i] = tau^i zt / delta, i < 2^log_m - 1"""
+    sc = [_np64(x) for x in (alpha, beta, gamma, delta, tau, zt)]
+    _check(_lib().zk_groth16_key_scalars_device(field_id(field), _ptr(d_u), _ptr(d_v), _ptr(d_w), int(d_u.shape[0]), int(num_inputs), int(log_m),
+                                                *[_ptr(x) for x in sc], _ptr(d_abc), _ptr(d_h) if int(d_h.shape[0]) else None,
+                                                ctypes.c_void_p(stream)), "zk_groth16_key_scalars_device")
+    return d_abc, d_h
+
+
+def _on_emulator():
+    return backend_info().startswith("emu")
+
+
+def _new_buffer(shape):
+    """zero device buffer of u64 limbs: a torch tensor on the GPU (numpy under the CPU test emulator, whose device memory is host memory)"""
+    if _on_emulator():
+        return np.zeros(shape, dtype=np.uint64)
+    import torch
+    return torch.zeros(shape, dtype=torch.int64, device="cuda")
+
+
+def _upload(arr):
+    arr = _np64(arr)
+    if _on_emulator():
+        return arr.copy()
+    import torch
+    return torch.from_numpy(arr.view(np.int64)).cuda()
+
+
+def _download(buf):
+    if isinstance(buf, np.ndarray):
+        return buf
+    import torch
+    torch.cuda.synchronize()
+    return buf.cpu().numpy().view(np.uint64)
+
+
+def _synchronize():
+    if not _on_emulator():
+        import torch
+        torch.cuda.synchronize()
+
+
+class Parameters:
+    """ark-groth16 0.3 ProvingKey<E> as generate_parameters leaves it, the point vectors resident on the device.  Offers what
+    `Prover` asks of a key (`points`, `upload`, `count`), so a prover can be built from it without a round trip through bytes."""
+
+    def __init__(self, pairing, num_inputs, device_members):
+        self.pairing, self.num_inputs, self.device = ark_serialize.pairing_id(pairing), num_inputs, device_members
+        self._host = {}
+
+    def _curve(self, name):
+        return ark_serialize.PAIRING_CURVES[self.pairing][1 if name in ark_serialize.G2_MEMBERS else 0]
+
+    def count(self, name):
+        return int(self.device[name].shape[0])
+
+    def points(self, name):
+        """member `name` as host limbs [count, 2 * limbs] (copied from the device once)"""
+        if name not in self._host:
+            self._host[name] = np.ascontiguousarray(_download(self.device[name])).reshape(self.count(name), -1)
+        return self._host[name]
+
+    def upload(self, name, skip_first=0):
+        """-> Bases over the resident member (zk_bases_adopt_device: no copy); skip_first as ProvingKey.upload"""
+        return Bases(self._curve(name), device_tensor=self.device[name][skip_first:], n=self.count(name) - skip_first)
+
+    def members(self):
+        return {name: self.points(name) for name in ark_serialize.PK_MEMBERS}
+
+    def serialize_unchecked(self):
+        """the bytes of ProvingKey::serialize_unchecked: the key file the reference's `compile` writes (lib/src/utils.rs:85-102)"""
+        return ark_serialize.ProvingKey.serialize_unchecked(self.pairing, self.members())
+
+    def verifying_key_bytes(self):
+        """ark_to_bytes(pk.vk): compressed"""
+        return ark_serialize.verifying_key_to_bytes(self.pairing, {name: self.points(name) for name in ark_serialize.VK_MEMBERS})
+
+
+def generate_parameters(pairing, A, B, C, num_inputs, n_vars, alpha, beta, gamma, delta, tau, g1=None, g2=None, stream=0):
+    """ark-groth16 0.3 generate_parameters from the resident R1CS matrices (A, B, C: R1csMatrix) and a given trapdoor (Montgomery
+    limbs).  g1 / g2: the group generators as affine Montgomery points, None = the curves' standard generators (upstream draws
+    random ones).  All per-element work runs on the device, on `stream`; returns Parameters once it has finished."""
+    pairing = ark_serialize.pairing_id(pairing)
+    field = "Bls381Fr" if pairing == ark_serialize.BLS12_381 else "Bn254Fr"
+    c1, c2 = ark_serialize.PAIRING_CURVES[pairing]
+    m, log_m = 1, 0
+    while m < A.n_rows + num_inputs:
+        m, log_m = 2 * m, log_m + 1
+    d_u, d_v, d_w = (_new_buffer((n_vars, 4)) for _ in range(3))
+    zt = qap_at(field, A, B, C, num_inputs, log_m, tau, d_u, d_v, d_w, stream=stream)
+    d_h = _new_buffer((m - 1, 4))
+    key_scalars(field, d_u, d_v, d_w, num_inputs, log_m, alpha, beta, gamma, delta, tau, zt, d_w, d_h, stream=stream)   # abc over w
+    d_s1, d_s2 = _upload(np.stack([_np64(alpha), _np64(beta), _np64(delta)])), _upload(np.stack([_np64(beta), _np64(gamma), _np64(delta)]))
+    l1, l2 = 2 * base_limbs(c1), 2 * base_limbs(c2)
+
+    def fixed_base(curve, base, d_scalars, limbs):
+        out = _new_buffer((int(d_scalars.shape[0]), limbs))
+        fixed_base_msm_device(curve, d_scalars, out, int(d_scalars.shape[0]), base=base, montgomery=True, stream=stream)
+        return out
+
+    p_s1, p_s2 = fixed_base(c1, g1, d_s1, l1), fixed_base(c2, g2, d_s2, l2)
+    p_a, p_b1, p_b2 = fixed_base(c1, g1, d_u, l1), fixed_base(c1, g1, d_v, l1), fixed_base(c2, g2, d_v, l2)
+    p_h, p_abc = fixed_base(c1, g1, d_h, l1), fixed_base(c1, g1, d_w, l1)
+    _synchronize()      # the scalar buffers go out of scope here
+    return Parameters(pairing, num_inputs, {
+        "alpha_g1": p_s1[0:1], "beta_g1": p_s1[1:2], "delta_g1": p_s1[2:3], "beta_g2": p_s2[0:1], "gamma_g2": p_s2[1:2], "delta_g2": p_s2[2:3],
+        "gamma_abc_g1": p_abc[:num_inputs], "l_query": p_abc[num_inputs:], "a_query": p_a, "b_g1_query": p_b1, "b_g2_query": p_b2,
+        "h_query": p_h})
+
+
+def generate_random_parameters(pairing, A, B, C, num_inputs, n_vars, g1=None, g2=None, stream=0):
+    """generate_random_parameters: alpha, beta, gamma, delta, tau from the operating system's generator (`secrets`), nonzero, tau
+    outside the evaluation domain (upstream: sample_element_outside_domain)"""
+    pairing = ark_serialize.pairing_id(pairing)
+    field = "Bls381Fr" if pairing == ark_serialize.BLS12_381 else "Bn254Fr"
+    p = field_modulus(field)
+    m = 1
+    while m < A.n_rows + num_inputs:
+        m *= 2
+    draw = lambda: 1 + secrets.randbelow(p - 1)
+    tau = draw()
+    while pow(tau, m, p) == 1:
+        tau = draw()
+    ints = [draw() for _ in range(4)] + [tau]
+    mont = ark_serialize.scalars_from_bytes(field, b"".join(v.to_bytes(32, "little") for v in ints), 5)
+    return generate_parameters(pairing, A, B, C, num_inputs, n_vars, mont[0], mont[1], mont[2], mont[3], mont[4], g1=g1, g2=g2, stream=stream)

@@ -100,6 +100,40 @@ typedef struct {
 int zk_groth16_assemble_proof(zk_pairing_t p, const zk_groth16_assembly *in, void *a_g1_affine_out, void *b_g2_affine_out,
                               void *c_g1_affine_out);
 
+/* ---- Groth16 key generation (ark-groth16 0.3 generator.rs generate_parameters; the reference's `compile` reaches it through
+ * Groth16::setup at lib/src/zk/encryption.rs:169, sample_entries.rs:141, property.rs:192) ----
+ * From the resident matrices to the scalars of the key's point vectors; the points themselves are zk_fixed_base_msm_device over
+ * those scalars (scalars_are_montgomery = 1).  Device buffers of Montgomery elements, trapdoor scalars in host memory.
+ * Every entry refuses with ZK_ERR_INVALID_ARG before it launches anything and leaves the library usable.
+ *
+ * out[j] = sum_{i < min(x_len, n_rows)} M[i][j] x[i] for j < n_cols, 0 for n_cols <= j < out_len (out_len >= n_cols): the product
+ * with the TRANSPOSED matrix -- upstream walks the rows and scatters `u[index] += coeff * x[i]`.  There are no 256-bit field
+ * atomics, so this is a gather over a column-major copy of the matrix, which the first such call on a handle builds on the
+ * device (histogram of col_idx, scan, scatter; synchronises hip_stream once) and zk_r1cs_matrix_free releases. */
+int zk_r1cs_matvec_transposed_device(uint64_t matrix, const void *x_mont_dev, uint64_t x_len, void *out_mont_dev, uint64_t out_len,
+                                     void *hip_stream);
+/* ark-poly 0.3 Radix2EvaluationDomain::evaluate_all_lagrange_coefficients(tau) on the size-2^log_m domain, tau outside it:
+ *   out[i] = L_i(tau) = (tau^m - 1) / m * w^i / (tau - w^i), i < m;  zt_out_host (optional) = tau^m - 1 = evaluate_vanishing_polynomial.
+ * tau^m = 1 is refused (upstream samples tau outside the domain; that branch is not provided). */
+int zk_lagrange_coefficients_device(zk_field_t f, uint32_t log_m, const void *tau_mont_host, void *out_dev, void *zt_out_mont_host,
+                                    void *hip_stream);
+/* r1cs_to_qap.rs LibsnarkReduction::instance_map_with_evaluation: with L = the Lagrange coefficients at tau (stream scratch),
+ *   u[j] = sum_i A[i][j] L_i + (j < num_inputs ? L_{num_constraints + j} : 0),  v[j] = sum_i B[i][j] L_i,  w[j] = sum_i C[i][j] L_i
+ * for j < n_vars (n_vars >= every matrix's n_cols; the tail is zero).  Same preconditions as zk_groth16_witness_map_r1cs_device:
+ * equal row counts, num_constraints + num_inputs <= 2^log_m; num_inputs <= n_vars. */
+int zk_groth16_qap_at_device(zk_field_t f, uint64_t matrix_a, uint64_t matrix_b, uint64_t matrix_c, uint64_t num_inputs, uint32_t log_m,
+                             const void *tau_mont_host, void *u_dev, void *v_dev, void *w_dev, uint64_t n_vars, void *zt_out_mont_host,
+                             void *hip_stream);
+/* generate_parameters, the scalars that are not u or v themselves (a_query = u, b_g1_query = b_g2_query = v):
+ *   abc_dev[j] = (beta u[j] + alpha v[j] + w[j]) / gamma for j < num_inputs (gamma_abc_g1), / delta for the rest (l_query), n_vars
+ *                elements in one pass; abc_dev may be one of u_dev, v_dev, w_dev;
+ *   h_dev[i]   = tau^i * zt / delta, i < 2^log_m - 1 (h_query).
+ * gamma = 0, delta = 0 or zt = 0 is refused (upstream unwraps the inverses). */
+int zk_groth16_key_scalars_device(zk_field_t f, const void *u_dev, const void *v_dev, const void *w_dev, uint64_t n_vars, uint64_t num_inputs,
+                                  uint32_t log_m, const void *alpha_mont_host, const void *beta_mont_host, const void *gamma_mont_host,
+                                  const void *delta_mont_host, const void *tau_mont_host, const void *zt_mont_host, void *abc_dev,
+                                  void *h_dev, void *hip_stream);
+
 /* ---- halo2_proofs 0.2 prover steps beyond commit / FFT, device buffers, Montgomery elements ----
  * The reference's circuit (circuits-halo2/src/encryption.rs:83-161: 13 advice + 8 fixed columns, a lookup table, a
  * permutation over the equality-enabled columns) is the shape donor; these are the per-row products a create_proof over

@@ -224,6 +224,17 @@ extern "C" {
                                               hip_stream: *mut c_void) -> c_int;
     pub fn zk_groth16_assemble_proof(p: c_int, input: *const zk_groth16_assembly, a_g1_affine_out: *mut c_void, b_g2_affine_out: *mut c_void,
                                      c_g1_affine_out: *mut c_void) -> c_int;
+    pub fn zk_r1cs_matvec_transposed_device(matrix: u64, x_mont_dev: *const c_void, x_len: u64, out_mont_dev: *mut c_void, out_len: u64,
+                                            hip_stream: *mut c_void) -> c_int;
+    pub fn zk_lagrange_coefficients_device(f: c_int, log_m: u32, tau_mont_host: *const c_void, out_dev: *mut c_void,
+                                           zt_out_mont_host: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn zk_groth16_qap_at_device(f: c_int, matrix_a: u64, matrix_b: u64, matrix_c: u64, num_inputs: u64, log_m: u32,
+                                    tau_mont_host: *const c_void, u_dev: *mut c_void, v_dev: *mut c_void, w_dev: *mut c_void, n_vars: u64,
+                                    zt_out_mont_host: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn zk_groth16_key_scalars_device(f: c_int, u_dev: *const c_void, v_dev: *const c_void, w_dev: *const c_void, n_vars: u64,
+                                         num_inputs: u64, log_m: u32, alpha_mont_host: *const c_void, beta_mont_host: *const c_void,
+                                         gamma_mont_host: *const c_void, delta_mont_host: *const c_void, tau_mont_host: *const c_void,
+                                         zt_mont_host: *const c_void, abc_dev: *mut c_void, h_dev: *mut c_void, hip_stream: *mut c_void) -> c_int;
     pub fn zk_batch_invert_device(f: c_int, a_dev: *mut c_void, n: u64, hip_stream: *mut c_void) -> c_int;
     pub fn zk_prefix_product_device(f: c_int, in_dev: *const c_void, out_dev: *mut c_void, n: u64, first_mont_host: *const c_void,
                                     total_out_mont_host: *mut c_void, hip_stream: *mut c_void) -> c_int;
