@@ -34,6 +34,7 @@ EXPORTS = [
     "zk_fixed_base_msm_device", "zk_ntt_extend_device", "zk_init_devices", "zk_device_count", "zk_msm_submit", "zk_msm_collect",
     "zk_msm_batch_device", "zk_ntt_configure", "zk_msm_profile_totals", "zk_ntt_profile_enable", "zk_ntt_profile_read",
     "zk_field_modulus", "zk_vec_scale_periodic_device", "zk_bases_refresh", "zk_bases_precompute", "zk_ntt_oop_device",
+    "zk_ntt_points_device", "zk_ntt_points",
 ]
 
 
@@ -118,6 +119,8 @@ def load(path=None):
     lib.zk_ntt_coset_device.argtypes = [i32, vp, ctypes.c_uint32, vp, i32, vp, vp, vp]
     lib.zk_ntt_extend_device.argtypes = [i32, vp, ctypes.c_uint32, ctypes.c_uint32, vp, i32, vp, vp, vp]
     lib.zk_ntt_oop_device.argtypes = [i32, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, i32, vp, vp, vp]
+    lib.zk_ntt_points_device.argtypes = [i32, vp, vp, ctypes.c_uint32, vp, i32, vp]
+    lib.zk_ntt_points.argtypes = [i32, vp, ctypes.c_uint32, vp, i32]
     lib.zk_coset_mul.argtypes = [i32, vp, ctypes.c_uint32, vp]
     lib.zk_coset_mul_device.argtypes = [i32, vp, ctypes.c_uint32, vp, vp]
     lib.zk_field_root_of_unity.argtypes = [i32, ctypes.c_uint32, vp]
@@ -440,6 +443,28 @@ def ntt(field, a, omega, scale_by_n_inv=False, stream=0, coset_pre=None, coset_p
                                        _ptr(gp) if gp is not None else None, _ptr(gq) if gq is not None else None,
                                        ctypes.c_void_p(stream)), "zk_ntt_coset_device")
     return a
+
+
+NTT_POINTS_MAX_LOG_N = 24   # ZK_NTT_POINTS_MAX_LOG_N
+
+
+def ntt_points_device(curve, d_src, d_dst, log_n, omega, scale_by_n_inv=False, stream=0):
+    """d_dst[i] = sum_j [omega^(i j)] d_src[j] (times n^-1 when scale_by_n_inv) over 2^log_n affine points of Pallas or Vesta
+    (device buffers, Montgomery, identity = (0, 0); d_src may be d_dst): halo2 best_fft with G = the curve.  omega: a
+    2^log_n-th root of unity of the curve's scalar field, Montgomery limbs on the host.  Does not synchronise."""
+    om = _np64(omega)
+    _check(load().zk_ntt_points_device(curve_id(curve), _ptr(d_src), _ptr(d_dst), int(log_n), _ptr(om), int(bool(scale_by_n_inv)),
+                                       ctypes.c_void_p(stream)), "zk_ntt_points_device")
+    return d_dst
+
+
+def ntt_points(curve, jacobian, log_n, omega, scale_by_n_inv=False):
+    """the same transform over host points: numpy uint64 [2^log_n, 12] Jacobian (x, y, z) Montgomery, z = 0 the identity;
+    returns a new array with every z = 1 (Montgomery) or (0, 1, 0) for the identity"""
+    buf = _np64(jacobian).copy()
+    om = _np64(omega)
+    _check(load().zk_ntt_points(curve_id(curve), _ptr(buf), int(log_n), _ptr(om), int(bool(scale_by_n_inv))), "zk_ntt_points")
+    return buf
 
 
 def coset_mul(field, a, g, stream=0):

@@ -1592,6 +1592,26 @@ API int zk_ipa_fold_bases_device(zk_curve_t c, void* g_aff, uint64_t half, const
     });
     return ZK_ERR_INVALID_ARG;
 }
+API int zk_ntt_points_device(zk_curve_t c, const void* src, void* dst, uint32_t log_n, const void* omega, int scale, void* stream) {
+    if (!src || !dst || !omega || !aligned16(src) || !aligned16(dst) || log_n > ZK_NTT_POINTS_MAX_LOG_N) return ZK_ERR_INVALID_ARG;
+    DEVICE_ENTRY(dst);
+    CURVE_SWITCH(c, {
+        Fe<typename C::Fr> w;
+        host_load(w, omega);
+        return ntt_points_run<C>(dc, (const Affine<C>*)src, (Affine<C>*)dst, log_n, w, scale ? 1 : 0, (hipStream_t)stream);
+    });
+    return ZK_ERR_INVALID_ARG;
+}
+API int zk_ntt_points(zk_curve_t c, void* jac, uint32_t log_n, const void* omega, int scale) {
+    if (!jac || !omega || log_n > ZK_NTT_POINTS_MAX_LOG_N) return ZK_ERR_INVALID_ARG;
+    DEVICE_ENTRY(nullptr);
+    CURVE_SWITCH(c, {
+        Fe<typename C::Fr> w;
+        host_load(w, omega);
+        return ntt_points_host_run<C>(dc, jac, log_n, w, scale ? 1 : 0);
+    });
+    return ZK_ERR_INVALID_ARG;
+}
 API int zk_ipa_collapse_device(zk_curve_t c, uint64_t handle, const void* w, uint64_t m0, uint64_t cur, void* g_out, void* stream) {
     return zk_ipa_collapse_range_device(c, handle, w, m0, cur, 0, cur, g_out, stream);
 }

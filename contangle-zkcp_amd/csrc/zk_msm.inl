@@ -602,9 +602,10 @@ int fixed_base_msm_run(DeviceCtx& dc, const Affine<C>& base, const Fe<typename C
     HIP_TRY(hipGetLastError());
     return ZK_OK;
 }
-// ---- GLV decomposition of the fold's shared scalar (host, 64-bit limbs; constants from tools/gen_glv.py) ----
+// ---- GLV decomposition of a scalar (64-bit limbs; constants from tools/gen_glv.py): on the host for the fold's shared scalar, in
+// ecfft_twiddle_kernel for the twiddles of the point FFT ----
 namespace glv {
-inline void mul_lo256(uint64_t* r, const uint64_t* a, const uint64_t* b) {   // (a * b) mod 2^256
+ZK_HD void mul_lo256(uint64_t* r, const uint64_t* a, const uint64_t* b) {   // (a * b) mod 2^256
     uint64_t t[4] = {0, 0, 0, 0};
     for (int i = 0; i < 4; i++) {
         unsigned __int128 c = 0;
@@ -616,7 +617,7 @@ inline void mul_lo256(uint64_t* r, const uint64_t* a, const uint64_t* b) {   // 
     }
     for (int i = 0; i < 4; i++) r[i] = t[i];
 }
-inline void sub256(uint64_t* r, const uint64_t* a, const uint64_t* b) {
+ZK_HD void sub256(uint64_t* r, const uint64_t* a, const uint64_t* b) {
     unsigned __int128 br = 0;
     for (int i = 0; i < 4; i++) {
         unsigned __int128 x = (unsigned __int128)a[i] - b[i] - (uint64_t)br;
@@ -624,12 +625,12 @@ inline void sub256(uint64_t* r, const uint64_t* a, const uint64_t* b) {
         br = (x >> 64) & 1;
     }
 }
-inline void neg256(uint64_t* r, const uint64_t* a) {
+ZK_HD void neg256(uint64_t* r, const uint64_t* a) {
     const uint64_t z[4] = {0, 0, 0, 0};
     sub256(r, z, a);
 }
 // c = (k * g) >> 384 for k < 2^256, g < 2^320
-inline void mulhi384(uint64_t* c, const uint64_t* k, const uint64_t* g5) {
+ZK_HD void mulhi384(uint64_t* c, const uint64_t* k, const uint64_t* g5) {
     uint64_t t[9] = {0};
     for (int i = 0; i < 4; i++) {
         unsigned __int128 cy = 0;
@@ -648,7 +649,7 @@ inline void mulhi384(uint64_t* c, const uint64_t* k, const uint64_t* g5) {
 }  // namespace glv
 
 template <class C>
-bool glv_decompose(const Fe<typename C::Fr>& u_canonical, FoldScalar& out) {
+ZK_HD bool glv_decompose(const Fe<typename C::Fr>& u_canonical, FoldScalar& out) {
     if constexpr (Glv<C>::HAS) {
         using G = Glv<C>;
         uint64_t k[4], c1[4], c2[4], t[4], k1[4], k2[4];
@@ -809,3 +810,4 @@ int ipa_collapse_run(DeviceCtx& dc, const BasesCopy& bc, uint64_t base_n, const 
     return ZK_OK;
 }
 }  // namespace zk
+#include "zk_ecfft.inl"

@@ -21,4 +21,9 @@ int ipa_fold_bases_run(DeviceCtx& dc, Affine<C>* g, uint64_t half, const Fe<type
 template <class C>
 int ipa_collapse_run(DeviceCtx& dc, const BasesCopy& bc, uint64_t base_n, const Fe<typename C::Fr>* w_dev, uint64_t m0, uint64_t cur, uint64_t first,
                      uint64_t count, Affine<C>* g_out, hipStream_t st);
+// the DFT of a vector of curve points (zk_ecfft_kernels.h): Pallas and Vesta, ZK_ERR_UNSUPPORTED elsewhere
+template <class C>
+int ntt_points_run(DeviceCtx& dc, const Affine<C>* src, Affine<C>* dst, uint32_t logn, const Fe<typename C::Fr>& omega_mont, int scale, hipStream_t st);
+template <class C>
+int ntt_points_host_run(DeviceCtx& dc, void* jac_host, uint32_t logn, const Fe<typename C::Fr>& omega_mont, int scale);
 }  // namespace zk

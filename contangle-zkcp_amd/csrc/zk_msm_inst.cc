@@ -10,4 +10,6 @@ template int bases_precompute_run<ZK_CURVE>(BasesCopy&, uint64_t, int);
 template int ipa_fold_bases_run<ZK_CURVE>(DeviceCtx&, Affine<ZK_CURVE>*, uint64_t, const Fe<ZK_CURVE::Fr>&, hipStream_t);
 template int ipa_collapse_run<ZK_CURVE>(DeviceCtx&, const BasesCopy&, uint64_t, const Fe<ZK_CURVE::Fr>*, uint64_t, uint64_t, uint64_t, uint64_t, Affine<ZK_CURVE>*,
                                         hipStream_t);
+template int ntt_points_run<ZK_CURVE>(DeviceCtx&, const Affine<ZK_CURVE>*, Affine<ZK_CURVE>*, uint32_t, const Fe<ZK_CURVE::Fr>&, int, hipStream_t);
+template int ntt_points_host_run<ZK_CURVE>(DeviceCtx&, void*, uint32_t, const Fe<ZK_CURVE::Fr>&, int);
 }  // namespace zk

@@ -15,7 +15,7 @@ import ctypes
 import numpy as np
 
 from . import (Bases, ZkError, _check, _np64, _ptr, base_limbs, curve_id, field_id, field_inverse, field_modulus, load, msm, msm_batch, msm_submit,
-               multiplicative_generator, ntt, root_of_unity, scalar_field, vec_op)
+               multiplicative_generator, ntt, ntt_points_device, root_of_unity, scalar_field, vec_op)
 
 PROVER_EXPORTS = ["zk_batch_invert_device", "zk_prefix_product_device", "zk_halo2_permutation_product_device",
                   "zk_halo2_lookup_product_device", "zk_halo2_permute_expression_pair_device", "zk_inner_product_device", "zk_vec_fold_device", "zk_ipa_fold_bases_device",
@@ -42,6 +42,60 @@ def best_fft(field, a, omega, log_n):
     if int(a.shape[0]) != 1 << log_n:
         raise AssertionError("assertion failed: a.len() == 1 << log_n")
     return ntt(field, a, omega)
+
+
+def best_fft_points(curve, d_points, omega, log_n, out=None, stream=0):
+    """best_fft(a, omega, log_n) with G = a curve (Pallas, Vesta): the DFT of 2^log_n affine points resident on the device with
+    scalar-field twiddles, no scaling.  In place, or into `out` with d_points left alone."""
+    if int(d_points.shape[0]) != 1 << log_n:
+        raise AssertionError("assertion failed: a.len() == 1 << log_n")
+    if out is not None and int(out.shape[0]) != 1 << log_n:
+        raise AssertionError("assertion failed: out.len() == 1 << log_n")
+    return ntt_points_device(curve, d_points, d_points if out is None else out, log_n, omega, False, stream)
+
+
+class Params:
+    """halo2_proofs 0.2 poly/commitment.rs Params<C>, the part that lives on the device: k, n, g and g_lagrange as resident
+    bases.  `from_g` does what Params::new does after it has hashed g: g_lagrange = best_fft(g, omega_k^-1) times n^-1,
+    normalised, i.e. g_lagrange[i] = [1/n] sum_j [omega^(-ij)] g_j, the key for which commit_lagrange(evals) ==
+    commit(coeffs).  Generating g itself (hash_to_curve("Halo2-Parameters"): BLAKE2b, simplified SWU, isogeny) is not done
+    here and stays with the caller, and so do w and u."""
+
+    def __init__(self, curve, k, d_g, d_g_lagrange):
+        self.curve, self.k, self.n = curve_id(curve), int(k), 1 << int(k)
+        self.d_g, self.d_g_lagrange = d_g, d_g_lagrange
+        self.g = Bases(curve, device_tensor=d_g, n=self.n)                    # zk_bases_adopt_device: no copy
+        self.g_lagrange = Bases(curve, device_tensor=d_g_lagrange, n=self.n)
+
+    @classmethod
+    def from_g(cls, curve, k, g, stream=0):
+        """g: 2^k affine points (Montgomery u64 limbs [n, 8], identity = (0, 0)), a host array or a device tensor"""
+        from .groth16 import _new_buffer, _synchronize, _upload
+        n = 1 << int(k)
+        if int(g.shape[0]) != n:
+            raise AssertionError("assertion failed: g.len() == 1 << k")
+        d_g = _upload(g) if isinstance(g, np.ndarray) else g
+        field = scalar_field(curve)
+        omega_inv = field_inverse(field, root_of_unity(field, int(k)))
+        d_gl = _new_buffer(tuple(d_g.shape))
+        ntt_points_device(curve, d_g, d_gl, int(k), omega_inv, True, stream)
+        _synchronize()          # the adopted vectors are read by MSMs on any stream
+        return cls(curve, k, d_g, d_gl)
+
+    def commit(self, coeffs):
+        """commit(poly) without blinding: best_multiexp(coeffs, g); coeffs Montgomery, host or device"""
+        return best_multiexp(coeffs, self.g)
+
+    def commit_lagrange(self, evals):
+        """commit_lagrange(poly) without blinding: best_multiexp(evals, g_lagrange)"""
+        return best_multiexp(evals, self.g_lagrange)
+
+    def commit_lagrange_batch(self, columns, stream=0):
+        return best_multiexp_batch(columns, self.g_lagrange, stream=stream)
+
+    def free(self):
+        self.g.free()
+        self.g_lagrange.free()
 
 
 def coeff_to_extended(field, d_ext, k, omega_ext, zeta, stream=0):

@@ -214,6 +214,21 @@ int zk_ntt(zk_field_t f, void *a_mont_host, uint32_t log_n, const void *omega_mo
 int zk_ntt_device(zk_field_t f, void *a_mont_dev, uint32_t log_n, const void *omega_mont_host,
                   int scale_by_n_inv, void *hip_stream);
 
+/* The same transform over a vector of curve points with scalar-field twiddles, Pallas and Vesta (ZK_ERR_UNSUPPORTED for the other
+ * curves), log_n <= ZK_NTT_POINTS_MAX_LOG_N (ZK_ERR_INVALID_ARG above; the workspace is 128 bytes per point plus 40 per point for
+ * the split twiddles, ZK_ERR_OOM when it cannot be had):
+ * dst[i] = sum_j [omega^(i j)] src[j]  (times n^-1 when scale_by_n_inv), n = 2^log_n: halo2_proofs 0.2 arithmetic.rs best_fft
+ * with G = a curve, the call in poly/commitment.rs Params::new.  Affine Montgomery points, identity = (0, 0); src == dst allowed.
+ * omega_mont_host: a 2^log_n-th root of unity of the curve's scalar field (omega^-1 and scale = 1 give g_lagrange); its order is
+ * checked (omega^(n/2) == -1, omega == 1 for log_n = 0: ZK_ERR_INVALID_ARG otherwise).  Runs on the caller's stream, on the
+ * device of dst, and does not synchronise. */
+#define ZK_NTT_POINTS_MAX_LOG_N 24
+int zk_ntt_points_device(zk_curve_t c, const void *src_affine_dev, void *dst_affine_dev, uint32_t log_n,
+                         const void *omega_mont_host, int scale_by_n_inv, void *hip_stream);
+/* host points, in place, Jacobian (x, y, z) Montgomery as pasta's Ep / Eq hold them, z = 0 the identity; written back with
+ * z = 1 (Montgomery) or as (0, 1, 0).  What the patched best_fft<G = curve> calls. */
+int zk_ntt_points(zk_curve_t c, void *jacobian_host, uint32_t log_n, const void *omega_mont_host, int scale_by_n_inv);
+
 int zk_ntt_configure(const zk_ntt_opts *opts);   /* NULL restores the defaults */
 int zk_ntt_profile_enable(int on);
 int zk_ntt_profile_read(zk_ntt_totals *out);

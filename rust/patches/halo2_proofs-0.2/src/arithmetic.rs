@@ -55,7 +55,13 @@ pub fn best_multiexp_batch<C: CurveAffine>(columns_dev: *const core::ffi::c_void
 }
 
 pub fn best_fft<G: Group>(a: &mut [G], omega: G::Scalar, log_n: u32) {
-    // G = Fp / Fq: the library; G = a curve (Params::new, setup only): upstream
+    // G = Fp / Fq: zk_ntt; G = a Pasta curve (Params::new: g -> g_lagrange): zk_ntt_points; anything else, or small: the CPU body
+    if a.len() >= 1 << 12 && points_fft::<G, pasta_curves::EpAffine>(a, &omega, log_n, zk::ZK_PALLAS) {
+        return;
+    }
+    if a.len() >= 1 << 12 && points_fft::<G, pasta_curves::EqAffine>(a, &omega, log_n, zk::ZK_VESTA) {
+        return;
+    }
     if let Some(field) = scalar_field_of_group::<G>() {
         if a.len() >= 1 << 12 {
             zk::init_once();
@@ -153,10 +159,41 @@ pub(crate) fn curve_from_jacobian_limbs<C: CurveAffine>(j: &[u64]) -> C::Curve {
     let z = from_montgomery_limbs::<C::Base>(&j[8..12]);
     Option::from(C::Curve::new_jacobian(x, y, z)).expect("zkcp_amd returned a point off the curve")
 }
-/// `best_fft` is generic over halo2's `Group`; the library takes the case where the group IS its scalar field
+/// `best_fft` with G = the projective form of the Pasta curve C (Ep for EpAffine, Eq for EqAffine): the points go over as the
+/// Montgomery limbs of their Jacobian coordinates (`jacobian_coordinates` + `limbs_of`, no view of the struct's memory) and come
+/// back through `curve_from_jacobian_limbs`, which checks the curve equation.  false: G is not that curve, nothing was touched.
+fn points_fft<G: Group, C: CurveAffine>(a: &mut [G], omega: &G::Scalar, log_n: u32, curve: i32) -> bool {
+    use pasta_curves::arithmetic::CurveExt;
+    use std::any::Any;
+    if TypeId::of::<G>() != TypeId::of::<C::Curve>() {
+        return false;
+    }
+    assert_eq!(a.len(), 1usize << log_n);
+    // G and C::Curve are the same type (checked above): `downcast_ref` / `downcast_mut` on each element, not a cast of the slice
+    let w = match (omega as &dyn Any).downcast_ref::<C::Scalar>() {
+        Some(w) => limbs_of(w),
+        None => return false,
+    };
+    let mut flat = Vec::with_capacity(12 * a.len());
+    for p in a.iter() {
+        let p = (p as &dyn Any).downcast_ref::<C::Curve>().unwrap();
+        let (x, y, z) = p.jacobian_coordinates();
+        flat.extend_from_slice(&limbs_of(&x));
+        flat.extend_from_slice(&limbs_of(&y));
+        flat.extend_from_slice(&limbs_of(&z));
+    }
+    zk::init_once();
+    // halo2 semantics: no scaling -- Params::new multiplies by n^-1 itself
+    zk::check(unsafe { zk::zk_ntt_points(curve, flat.as_mut_ptr() as _, log_n, w.as_ptr() as _, 0) }, "zk_ntt_points").unwrap();
+    for (p, j) in a.iter_mut().zip(flat.chunks(12)) {
+        *(p as &mut dyn Any).downcast_mut::<C::Curve>().unwrap() = curve_from_jacobian_limbs::<C>(j);
+    }
+    true
+}
+/// `best_fft` is generic over halo2's `Group`; zk_ntt takes the case where the group IS its scalar field
 fn scalar_field_of_group<G: Group>() -> Option<i32> {
     if TypeId::of::<G>() != TypeId::of::<G::Scalar>() {
-        return None; // a curve: Params::new's FFT over points stays on the CPU
+        return None; // a curve: points_fft above
     }
     let m = <G::Scalar as PrimeField>::MODULUS;
     if m.ends_with("992d30ed00000001") {
@@ -168,7 +205,7 @@ fn scalar_field_of_group<G: Group>() -> Option<i32> {
     }
 }
 
-// ---- CPU paths for the inputs the library does not take (small sizes, other curves, FFTs over points).  Plain
+// ---- CPU paths for the inputs the library does not take (small sizes, other curves and groups).  Plain
 // single-threaded forms with the same results as upstream's; a maintainer who wants upstream's multi-threaded bodies for
 // these sizes keeps them under these names instead.
 fn cpu_best_multiexp<C: CurveAffine>(coeffs: &[C::Scalar], bases: &[C]) -> C::Curve {

@@ -172,6 +172,9 @@ extern "C" {
     pub fn zk_ntt(f: c_int, a_mont_host: *mut c_void, log_n: u32, omega_mont_host: *const c_void, scale_by_n_inv: c_int) -> c_int;
     pub fn zk_ntt_device(f: c_int, a_mont_dev: *mut c_void, log_n: u32, omega_mont_host: *const c_void, scale_by_n_inv: c_int,
                          hip_stream: *mut c_void) -> c_int;
+    pub fn zk_ntt_points_device(c: c_int, src_affine_dev: *const c_void, dst_affine_dev: *mut c_void, log_n: u32,
+                                omega_mont_host: *const c_void, scale_by_n_inv: c_int, hip_stream: *mut c_void) -> c_int;
+    pub fn zk_ntt_points(c: c_int, jacobian_host: *mut c_void, log_n: u32, omega_mont_host: *const c_void, scale_by_n_inv: c_int) -> c_int;
     pub fn zk_ntt_configure(opts: *const zk_ntt_opts) -> c_int;
     pub fn zk_ntt_profile_enable(on: c_int) -> c_int;
     pub fn zk_ntt_profile_read(out: *mut zk_ntt_totals) -> c_int;
