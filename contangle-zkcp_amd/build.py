@@ -13,6 +13,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libzkcp_amd.so")
 EMU_DIR = os.path.join(ROOT, "tests", "emu")
 EMU_LIB = os.path.join(EMU_DIR, "libzkcp_emu.so")
+PROBE_LIB = os.path.join(EMU_DIR, "libzk_field_probe.so")
 
 CURVES = ["Pallas", "Vesta", "Bn254G1", "Bls381G1", "Bn254G2", "Bls381G2"]
 FIELDS = ["PallasFp", "PallasFq", "Bn254Fr", "Bls381Fr"]
@@ -63,14 +64,14 @@ def _run(cmd, verbose):
     return r.stdout
 
 
-def _compile_all(base_cmd, objdir, extra_deps, verbose, jobs):
+def _compile_all(base_cmd, objdir, extra_deps, verbose, jobs, units=None, srcdir=CSRC):
     os.makedirs(objdir, exist_ok=True)
     objs, todo = [], []
-    for src, define, tag in UNITS:
+    for src, define, tag in (UNITS if units is None else units):
         obj = os.path.join(objdir, tag + ".o")
         objs.append(obj)
         if _newer(obj, _deps(obj) + extra_deps):
-            cmd = base_cmd + (["-D" + define] if define else []) + ["-MMD", "-MF", obj + ".d", "-c", os.path.join(CSRC, src), "-o", obj]
+            cmd = base_cmd + ["-D" + d for d in (define.split() if define else [])] + ["-MMD", "-MF", obj + ".d", "-c", os.path.join(srcdir, src), "-o", obj]
             todo.append(cmd)
     with concurrent.futures.ThreadPoolExecutor(max_workers=jobs) as ex:
         list(ex.map(lambda c: _run(c, verbose), todo))
@@ -116,9 +117,36 @@ def build_emu(force=False, verbose=False, sanitize=False, jobs=None):
     return out
 
 
+# the device probe of the field / curve primitives: one unit per field, one per curve and form, and the entry point
+PROBE_UNITS = [("field_probe.hip", None, "probe_entry")] + \
+              [("field_probe.hip", "ZK_PROBE_FIELD=%d" % i, "probe_f%d" % i) for i in range(6)] + \
+              [("field_probe.hip", "ZK_PROBE_CURVE=%d ZK_PROBE_FORM=%d" % (i, f), "probe_c%d_%d" % (i, f)) for i in range(len(CURVES)) for f in (1, 0)]
+
+
+def build_probe(force=False, verbose=False, jobs=None):
+    """TEST INFRASTRUCTURE: tests/emu/field_probe.hip (the op table of tests/emu/field_ops.h as gfx950 kernels) with the
+    compiler and the flags of the product units -- the point is the code this compiler makes for the primitives at the
+    product's optimisation level."""
+    probe_src = [os.path.join(EMU_DIR, "field_probe.hip"), os.path.join(EMU_DIR, "field_ops.h")]
+    if not force and not _newer(PROBE_LIB, _deps() + probe_src):
+        return PROBE_LIB
+    jobs = jobs or min(len(PROBE_UNITS), os.cpu_count() or 4)
+    objdir = os.path.join(PKG, "build", "probe")
+    if force:
+        shutil.rmtree(objdir, ignore_errors=True)
+    base = [hipcc_path(), "-x", "hip", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
+            "-fno-gpu-rdc", "-Wno-unused-result", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-I" + EMU_DIR]
+    objs = _compile_all(base, objdir, [], verbose, jobs, units=PROBE_UNITS, srcdir=EMU_DIR)
+    _run([hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC", "-fno-gpu-rdc", "-o", PROBE_LIB + ".tmp"] + objs, verbose)
+    os.replace(PROBE_LIB + ".tmp", PROBE_LIB)
+    return PROBE_LIB
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["hip"]
     if "hip" in what:
         print(build_hip(force="-f" in what, verbose=True))
     if "emu" in what:
         print(build_emu(force="-f" in what, verbose=True))
+    if "probe" in what:
+        print(build_probe(force="-f" in what, verbose=True))

@@ -7,6 +7,10 @@
 // It is NOT a backend: nothing in the product loads tests/emu/libzkcp_emu.so, bench.py and
 // __graft_entry__.smoke() never touch it, and the product library fails with ZK_ERR_NO_DEVICE
 // when no MI355X is present.
+//
+// Also in tests/emu/, equally test-only: field_ops.h (one op table of the field and curve primitives), f29_check.cc (its g++
+// runner, driven over stdin by tests/field_cases.py) and field_probe.hip (the same table as gfx950 kernels: the device probe
+// libzk_field_probe.so, built by build_probe() in contangle-zkcp_amd/build.py, driven by tests/test_field_probe_gpu.py).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

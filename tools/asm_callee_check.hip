@@ -2,6 +2,8 @@
 // values inside a NON-inlined callee -- 12-limb operands arrive through the stack -- as the portable product, with all
 // lanes active and under a divergent EXEC mask?  Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude
 // -Icontangle-zkcp_amd/csrc tools/asm_callee_check.hip -o tools/asm_callee_check ; prints mismatch counts.
+// Superseded for correctness by the device probe (tests/emu/field_probe.hip, tests/test_field_probe_gpu.py), which runs
+// fe_mul, fe_mul_portable and fe_mul_call on edge operands against Python integers; kept as the record of that diagnosis.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
