@@ -1477,6 +1477,116 @@ API int zk_halo2_permute_expression_pair_device(zk_field_t f, const void* inputs
     });
     return ZK_ERR_INVALID_ARG;
 }
+// ---- halo2 key generation: plonk/permutation/keygen.rs Assembly on the host (the walk of a cycle is sequential by definition),
+// the permutation columns on the device (zk_keygen.inl)
+namespace {
+// Assembly { mapping, aux, sizes } over ncols x n cells, cell (c, r) at c * n + r.  mapping holds col << 32 | row, the form
+// zk_halo2_assembly_mapping hands out; aux (the cycle's distinguished cell) and sizes are flat 32-bit cell indices / counts.
+struct Halo2Assembly {
+    uint64_t n = 0;
+    uint32_t ncols = 0;
+    std::vector<uint64_t> mapping;
+    std::vector<uint32_t> aux, sizes;
+    uint64_t flat(uint64_t packed) const { return (packed >> 32) * n + (packed & 0xffffffffull); }
+    // Assembly::copy; false = Error::BoundsFailure (nothing changed)
+    bool copy(uint32_t lc, uint32_t lr, uint32_t rc, uint32_t rr) {
+        if (lc >= ncols || rc >= ncols || lr >= n || rr >= n) return false;
+        uint64_t left = (uint64_t)lc * n + lr, right = (uint64_t)rc * n + rr;
+        if (aux[left] == aux[right]) return true;                    // already in the same cycle
+        if (sizes[aux[left]] < sizes[aux[right]]) std::swap(left, right);
+        sizes[aux[left]] += sizes[aux[right]];                       // the left cycle absorbs the right one
+        const uint32_t head = aux[left];
+        uint64_t i = right;
+        do {
+            aux[i] = head;
+            i = flat(mapping[i]);
+        } while (i != right);
+        std::swap(mapping[left], mapping[right]);
+        return true;
+    }
+};
+std::mutex g_asm_mu;
+std::map<uint64_t, std::unique_ptr<Halo2Assembly>> g_asms;
+uint64_t g_next_asm = 1;
+}  // namespace
+
+API int zk_halo2_assembly_new(uint64_t n, uint32_t ncols, uint64_t* handle_out) {
+    if (!handle_out || n == 0 || ncols == 0 || n > (1ull << 32) || n * ncols >= (1ull << 32)) return ZK_ERR_INVALID_ARG;
+    std::unique_ptr<Halo2Assembly> a;
+    const uint64_t cells = n * ncols;
+    try {
+        a.reset(new Halo2Assembly());
+        a->n = n;
+        a->ncols = ncols;
+        a->mapping.resize(cells);
+        a->aux.resize(cells);
+        a->sizes.assign(cells, 1u);
+    } catch (const std::bad_alloc&) {
+        return ZK_ERR_OOM;
+    }
+    for (uint32_t c = 0; c < ncols; c++)
+        for (uint64_t r = 0; r < n; r++) {
+            a->mapping[c * n + r] = ((uint64_t)c << 32) | r;
+            a->aux[c * n + r] = (uint32_t)(c * n + r);
+        }
+    std::lock_guard<std::mutex> lk(g_asm_mu);
+    const uint64_t h = g_next_asm++;
+    g_asms[h] = std::move(a);
+    *handle_out = h;
+    return ZK_OK;
+}
+API int zk_halo2_assembly_copy(uint64_t handle, const uint32_t* quads, uint64_t count, uint64_t* applied_out) {
+    if (applied_out) *applied_out = 0;
+    if (count && !quads) return ZK_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(g_asm_mu);
+    auto it = g_asms.find(handle);
+    if (it == g_asms.end()) return ZK_ERR_BAD_HANDLE;
+    Halo2Assembly& a = *it->second;
+    for (uint64_t q = 0; q < count; q++) {
+        if (!a.copy(quads[4 * q], quads[4 * q + 1], quads[4 * q + 2], quads[4 * q + 3])) return ZK_ERR_INVALID_ARG;
+        if (applied_out) *applied_out = q + 1;
+    }
+    return ZK_OK;
+}
+API int zk_halo2_assembly_mapping(uint64_t handle, void* mapping_out) {
+    if (!mapping_out) return ZK_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(g_asm_mu);
+    auto it = g_asms.find(handle);
+    if (it == g_asms.end()) return ZK_ERR_BAD_HANDLE;
+    memcpy(mapping_out, it->second->mapping.data(), it->second->mapping.size() * sizeof(uint64_t));
+    return ZK_OK;
+}
+API int zk_halo2_assembly_free(uint64_t handle) {
+    std::lock_guard<std::mutex> lk(g_asm_mu);
+    auto it = g_asms.find(handle);
+    if (it == g_asms.end()) return ZK_ERR_BAD_HANDLE;
+    g_asms.erase(it);
+    return ZK_OK;
+}
+API int zk_halo2_permutation_sigmas_device(zk_field_t f, uint32_t k, uint32_t ncols, const void* mapping_dev, const void* delta,
+                                           void* sigmas_dev, void* stream) {
+    if (!mapping_dev || !delta || !sigmas_dev || !aligned16(mapping_dev) || !aligned16(sigmas_dev) || ncols == 0 || k > 30)
+        return ZK_ERR_INVALID_ARG;
+    FIELD_SWITCH(f, {
+        if (k > (uint32_t)F::TWO_ADICITY) return ZK_ERR_INVALID_ARG;
+    });
+    if (((uint64_t)ncols << k) >= (1ull << 32)) return ZK_ERR_INVALID_ARG;       // the assembly's own limit on the number of cells
+    {   // 8 bytes per cell in, 32 out
+        const uintptr_t m0 = (uintptr_t)mapping_dev, s0 = (uintptr_t)sigmas_dev, cells = (uintptr_t)ncols << k;
+        if (m0 < s0 + cells * 32 && s0 < m0 + cells * 8) return ZK_ERR_INVALID_ARG;
+    }
+    DEVICE_ENTRY(sigmas_dev);
+    FIELD_SWITCH(f, {
+        Fe<F> d, w;
+        host_load(d, delta);
+        for (int i = 0; i < F::N; i++) w.v[i] = F::ROOT[i];
+        for (uint32_t i = k; i < (uint32_t)F::TWO_ADICITY; i++) fe_sqr(w, w);
+        int bad = 0;
+        ZK_TRY(perm_sigmas_run<F>(dc, (int)f, k, ncols, (const uint64_t*)mapping_dev, d, w, (Fe<F>*)sigmas_dev, &bad, (hipStream_t)stream));
+        return bad ? ZK_ERR_INVALID_ARG : ZK_OK;
+    });
+    return ZK_ERR_INVALID_ARG;
+}
 API int zk_inner_product_device(zk_field_t f, const void* a, const void* b, uint64_t n, void* out_host, void* stream) {
     if (!out_host || (n && (!a || !b || !aligned16(a) || !aligned16(b)))) return ZK_ERR_INVALID_ARG;
     DEVICE_ENTRY(a);

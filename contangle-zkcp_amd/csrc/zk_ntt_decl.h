@@ -95,6 +95,10 @@ template <class F>
 int groth16_key_scalars_run(DeviceCtx& dc, const Fe<F>* u, const Fe<F>* v, const Fe<F>* w, uint64_t n_vars, uint64_t num_inputs, uint32_t logm,
                             const Fe<F>& alpha, const Fe<F>& beta, const Fe<F>& gamma, const Fe<F>& delta, const Fe<F>& tau, const Fe<F>& zt,
                             Fe<F>* abc, Fe<F>* h, hipStream_t st);
+// halo2 key generation (zk_keygen.inl)
+template <class F>
+int perm_sigmas_run(DeviceCtx& dc, int field, uint32_t k, uint32_t ncols, const uint64_t* mapping, const Fe<F>& delta, const Fe<F>& omega,
+                    Fe<F>* sigmas, int* bad_mapping, hipStream_t st);
 template <class F>
 int witness_map_run(DeviceCtx& dc, int field, Fe<F>* a, Fe<F>* b, Fe<F>* c, uint32_t logm, hipStream_t st);
 }  // namespace zk

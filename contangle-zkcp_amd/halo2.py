@@ -21,7 +21,9 @@ PROVER_EXPORTS = ["zk_batch_invert_device", "zk_prefix_product_device", "zk_halo
                   "zk_halo2_lookup_product_device", "zk_halo2_permute_expression_pair_device", "zk_inner_product_device", "zk_vec_fold_device", "zk_ipa_fold_bases_device",
                   "zk_expr_eval_device", "zk_ipa_virtual_scalars_device", "zk_ipa_update_weights_device", "zk_ipa_collapse_device", "zk_ipa_collapse_range_device", "zk_ipa_round_device",
                   "zk_poly_eval_device", "zk_poly_eval_batch_device", "zk_vec_muladd_device", "zk_vec_muladd_to_device", "zk_kate_division_device", "zk_vec_powers_device", "zk_vec_fold_many_device",
-                  "zk_ipa_fold_round_device", "zk_expr_eval_lazy_device", "zk_expr_configure", "zk_expr_specialised_source"]
+                  "zk_ipa_fold_round_device", "zk_expr_eval_lazy_device", "zk_expr_configure", "zk_expr_specialised_source",
+                  "zk_halo2_assembly_new", "zk_halo2_assembly_copy", "zk_halo2_assembly_mapping", "zk_halo2_assembly_free",
+                  "zk_halo2_permutation_sigmas_device"]
 
 
 def best_multiexp(coeffs, bases):
@@ -348,6 +350,11 @@ def _plib():
     lib.zk_expr_eval_lazy_device.argtypes = [i32, ctypes.POINTER(ExprOp), u32, pp, u32, vp, u32, u32, u32, vp, vp]
     lib.zk_expr_configure.argtypes = [i32]
     lib.zk_expr_specialised_source.argtypes = [i32, ctypes.POINTER(ExprOp), u32, u32, u32, ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+    lib.zk_halo2_assembly_new.argtypes = [u64, u32, ctypes.POINTER(u64)]
+    lib.zk_halo2_assembly_copy.argtypes = [u64, vp, u64, ctypes.POINTER(u64)]
+    lib.zk_halo2_assembly_mapping.argtypes = [u64, vp]
+    lib.zk_halo2_assembly_free.argtypes = [u64]
+    lib.zk_halo2_permutation_sigmas_device.argtypes = [i32, u32, u32, vp, vp, vp, vp]
     return lib
 
 
@@ -763,3 +770,226 @@ class IpaProverVirtual:
     def folded_generator(self):
         """G' after the rounds so far are all done (n == 1): MSM(G0, W) -- what upstream's collapsed g_prime[0] is"""
         return msm(self.bases, self.W, montgomery=True, stream=self.stream)
+
+
+# ------------------------------------------------------------------ key generation (plonk/keygen.rs, plonk/permutation/keygen.rs)
+def delta(field):
+    """pasta_curves 0.4 `FieldExt::DELTA` = GENERATOR^(2^S), S the field's two-adicity (generator 5, S = 32 on both Pasta fields):
+    a generator of the odd-order subgroup, so the cosets delta^c H label the permutation argument's columns.  Montgomery limbs --
+    the `delta` argument of permutation_product."""
+    p = field_modulus(field)
+    g = multiplicative_generator(field)
+    gi = sum(int(w) << (64 * i) for i, w in enumerate(g.tolist())) * pow(1 << 256, -1, p) % p
+    s = ((p - 1) & -(p - 1)).bit_length() - 1
+    return _mont_limbs(pow(gi, 1 << s, p), p)
+
+
+class BoundsFailure(ValueError):
+    """upstream's Error::BoundsFailure from Assembly::copy; `applied` = how many copies of the call went in before it"""
+
+    def __init__(self, applied):
+        ValueError.__init__(self, "BoundsFailure: copy %d names a row or a column outside the permutation" % applied)
+        self.applied = applied
+
+
+class Assembly:
+    """plonk/permutation/keygen.rs Assembly over `ncols` columns of `n` rows: Assembly::new's identity mapping, then `copy` in the
+    caller's order -- the permutation depends on that order and is upstream's, cell for cell (the larger cycle absorbs the smaller,
+    the left one on a tie; mapping[left] and mapping[right] are swapped).  Lives in host memory inside the library: the walk of a
+    cycle is sequential by definition, and a Python loop per copy would take minutes at 2^24 cells.  Columns are the indices of
+    the permutation argument's column list (upstream looks the Column up there).  Which cells a circuit copies -- synthesis and
+    floor planning -- is the caller's business."""
+
+    def __init__(self, n, ncols):
+        h = ctypes.c_uint64(0)
+        _check(_plib().zk_halo2_assembly_new(int(n), int(ncols), ctypes.byref(h)), "zk_halo2_assembly_new")
+        self.handle, self.n, self.ncols = h.value, int(n), int(ncols)
+
+    def copy(self, left_column, left_row, right_column, right_row):
+        self.copy_many([(left_column, left_row, right_column, right_row)])
+
+    def copy_many(self, quads):
+        """quads: [count, 4] (left_column, left_row, right_column, right_row), applied in order; the first one out of bounds raises
+        BoundsFailure (its .applied = the number applied before it; the rest are not looked at).  Returns the number applied."""
+        # a value that does not fit 32 bits is out of bounds, not another cell: it becomes 2^32 - 1, which no assembly has
+        if isinstance(quads, np.ndarray) and quads.dtype.kind in "iu":
+            q = quads.reshape(-1, 4)
+            if q.dtype != np.uint32:
+                q = q if q.dtype == np.uint64 else q.astype(np.int64)
+                q = np.where((q < 0) | (q > 0xFFFFFFFF), 0xFFFFFFFF, q).astype(np.uint32)
+        else:
+            q = np.array([[v if 0 <= v < 1 << 32 else 0xFFFFFFFF for v in map(int, quad)] for quad in quads], dtype=np.uint32).reshape(-1, 4)
+        q = np.ascontiguousarray(q)
+        done = ctypes.c_uint64(0)
+        st = _plib().zk_halo2_assembly_copy(self.handle, _ptr(q), int(q.shape[0]), ctypes.byref(done))
+        if st == ZK_ERR_INVALID_ARG:
+            raise BoundsFailure(done.value)
+        _check(st, "zk_halo2_assembly_copy")
+        return done.value
+
+    def mapping(self):
+        """[ncols, n] uint64, mapping[c][r] = column << 32 | row of the cell (c, r) maps to"""
+        out = np.zeros((self.ncols, self.n), dtype=np.uint64)
+        _check(_plib().zk_halo2_assembly_mapping(self.handle, _ptr(out)), "zk_halo2_assembly_mapping")
+        return out
+
+    def free(self):
+        if self.handle:
+            _check(_plib().zk_halo2_assembly_free(self.handle), "zk_halo2_assembly_free")
+            self.handle = 0
+
+
+def permutation_sigmas(field, k, mapping, sigmas=None, stream=0):
+    """Assembly::build_vk / build_pk, the columns themselves: sigmas[c][j] = DELTA^col omega^row for mapping[c][j] = col << 32 | row
+    (zk_halo2_permutation_sigmas_device).  mapping: [ncols, 2^k] uint64, host (uploaded) or device; sigmas: device [ncols, 2^k, 4],
+    allocated when not given.  A mapping that names a cell outside the ncols x 2^k grid raises ZkError(ZK_ERR_INVALID_ARG)."""
+    from .groth16 import _new_buffer, _upload
+    ncols, n = int(mapping.shape[0]), int(mapping.shape[1])
+    if n != 1 << k:
+        raise AssertionError("assertion failed: mapping.len() == 1 << k")
+    d_map = _upload(mapping) if isinstance(mapping, np.ndarray) else mapping
+    sigmas = _new_buffer((ncols, n, 4)) if sigmas is None else sigmas
+    dl = delta(field)
+    _check(_plib().zk_halo2_permutation_sigmas_device(field_id(field), int(k), ncols, _ptr(d_map), _ptr(dl), _ptr(sigmas), ctypes.c_void_p(stream)),
+           "zk_halo2_permutation_sigmas_device")
+    return sigmas
+
+
+class PermutationVerifyingKey:
+    """plonk/permutation.rs VerifyingKey: commitments[c] = commit_lagrange(permutations[c]), host, Jacobian like msm()"""
+
+    def __init__(self, commitments):
+        self.commitments = commitments
+
+
+class PermutationProvingKey:
+    """plonk/permutation.rs ProvingKey, resident: permutations [ncols, n, 4] (Lagrange; the `sigmas` of permutation_product as it
+    is), polys [ncols, n, 4] (coefficients), cosets [ncols, extended_len, 4] or None"""
+
+    def __init__(self, permutations, polys, cosets):
+        self.permutations, self.polys, self.cosets = permutations, polys, cosets
+
+
+class VerifyingKey:
+    """plonk.rs VerifyingKey, the computed part: domain, fixed_commitments, permutation.commitments.  Upstream commits with
+    Blind::default(), which adds [1] W; `Params` here leaves w to the caller, so every commitment is the multi-scalar part only
+    (add W to each for upstream's points).  The key's transcript representation (hashing it into the transcript) is not built."""
+
+    def __init__(self, domain, fixed_commitments, permutation, blinding_factors):
+        self.domain, self.fixed_commitments, self.permutation, self.blinding_factors = domain, fixed_commitments, permutation, blinding_factors
+
+
+class ProvingKey:
+    """plonk.rs ProvingKey, resident on the device: fixed_values / fixed_polys [nfixed, n, 4], fixed_cosets [nfixed, extended_len, 4],
+    permutation (PermutationProvingKey), l0 / l_last / l_active_row [extended_len, 4] (None with cosets=None) and their
+    coefficient forms l0_poly / l_last_poly / l_active_row_poly [n, 4] (not kept upstream; a prover that evaluates the quotient
+    sub-coset by sub-coset extends from them)"""
+
+    def __init__(self, vk):
+        self.vk = vk
+        self.fixed_values = self.fixed_polys = self.fixed_cosets = self.permutation = None
+        self.l0 = self.l_last = self.l_active_row = self.l0_poly = self.l_last_poly = self.l_active_row_poly = None
+
+    def free(self):
+        """drop the resident buffers"""
+        ProvingKey.__init__(self, self.vk)
+
+
+def _fixed_values(field, n, fixed):
+    """the fixed columns as one resident [nfixed, n, 4] buffer; a (numerators, denominators) pair is batch_invert_assigned's
+    num / den with a zero denominator giving 0"""
+    from .groth16 import _new_buffer, _upload
+
+    def check(a):
+        if int(a.shape[0]) != n:
+            raise AssertionError("assertion failed: a.values.len() == 1 << self.k")
+        return a
+
+    def store(dst, src):
+        if isinstance(dst, np.ndarray):
+            dst[:] = _np64(src)
+        elif isinstance(src, np.ndarray):
+            import torch
+            dst.copy_(torch.from_numpy(_np64(src).view(np.int64)))
+        else:
+            dst.copy_(src)
+
+    out = _new_buffer((max(len(fixed), 1), n, 4))[:len(fixed)]
+    for i, col in enumerate(fixed):
+        if isinstance(col, (tuple, list)):
+            num, den = check(col[0]), check(col[1])
+            store(out[i], den)
+            batch_invert(field, out[i])
+            vec_op(field, "mul", out[i], b=_upload(num) if isinstance(num, np.ndarray) else num)
+        else:
+            store(out[i], check(col))
+    return out
+
+
+def _keygen_checks(params, asm, blinding_factors):
+    if asm.n != params.n:
+        raise AssertionError("assertion failed: assembly.n == params.n")
+    if params.n < blinding_factors + 3:          # upstream: cs.minimum_rows() -> Error::NotEnoughRowsAvailable
+        raise ValueError("NotEnoughRowsAvailable: n = %d < blinding_factors + 3 = %d" % (params.n, blinding_factors + 3))
+
+
+def keygen_vk(params, degree, fixed, asm, blinding_factors, stream=0):
+    """plonk/keygen.rs keygen_vk after synthesis: `fixed` = the fixed columns (selectors already compressed into them by the caller;
+    each a host or device [n, 4] Montgomery array, or a (numerators, denominators) pair of such -- upstream's Assigned cells),
+    `asm` = the permutation Assembly, `degree` = cs.degree().  Commitments are computed on the device over params.g_lagrange and
+    carry no blinding term (see VerifyingKey).  Out of scope: circuit synthesis and floor planning, compress_selectors, hashing
+    g / w / u, the verifying key's transcript representation."""
+    _keygen_checks(params, asm, blinding_factors)
+    field = scalar_field(params.curve)
+    domain = EvaluationDomain(field, degree, params.k)
+    values = _fixed_values(field, params.n, fixed)
+    nl = load().zk_curve_base_limbs64(params.curve)
+    fixed_commitments = params.commit_lagrange_batch(values, stream=stream) if len(fixed) else np.zeros((0, 3 * nl), dtype=np.uint64)
+    sigmas = permutation_sigmas(field, params.k, asm.mapping(), stream=stream)
+    return VerifyingKey(domain, fixed_commitments, PermutationVerifyingKey(params.commit_lagrange_batch(sigmas, stream=stream)), blinding_factors)
+
+
+def keygen_pk(params, vk, fixed, asm, cosets="mont", stream=0):
+    """plonk/keygen.rs keygen_pk after synthesis, the key resident on the device (ProvingKey): fixed_values -> fixed_polys
+    (lagrange_to_coeff) -> fixed_cosets (coeff_to_extended); the permutation columns likewise (Assembly::build_pk); l0 (row 0),
+    l_last (row n - blinding_factors - 1) and l_active_row = 1 - (l_last + l_blind) on the extended coset.  l_active_row is
+    computed as the extension of the active rows' indicator column: extension is linear and the constant 1 extends to 1, so that
+    is the same polynomial and the same canonical values as upstream's pass over three extended vectors.
+    cosets: "mont" = Montgomery form; "lazy" = the R' radix evaluate_expression(lazy=True) reads (ZK_NTT_OUT_R29; equal to
+    to_lazy_form of the "mont" result); None = no extended forms at all (27 x 256 MB at k = 20, extended_k = 23: a prover that
+    evaluates the quotient by sub-coset extends from the coefficient forms instead).
+    Out of scope: circuit synthesis and floor planning, compress_selectors, hashing g / w / u, the key's transcript representation."""
+    from .groth16 import _new_buffer
+    if cosets not in ("mont", "lazy", None):
+        raise ZkError(ZK_ERR_INVALID_ARG, "cosets must be \"mont\", \"lazy\" or None")
+    bf = vk.blinding_factors
+    _keygen_checks(params, asm, bf)
+    field, domain, n = vk.domain.field, vk.domain, params.n
+    ext = domain.extended_len()
+    lazy = cosets == "lazy"
+
+    def forms(values):
+        count = int(values.shape[0])
+        polys = _new_buffer((max(count, 1), n, 4))[:count]
+        ext_forms = _new_buffer((max(count, 1), ext, 4))[:count] if cosets else None
+        for i in range(count):
+            domain.lagrange_to_coeff(values[i], stream=stream, out=polys[i])
+            if cosets:
+                domain.coeff_to_extended(ext_forms[i], stream=stream, coeffs=polys[i], lazy_out=lazy)
+        return polys, ext_forms
+
+    pk = ProvingKey(vk)
+    pk.fixed_values = _fixed_values(field, n, fixed)
+    pk.fixed_polys, pk.fixed_cosets = forms(pk.fixed_values)
+    sigmas = permutation_sigmas(field, params.k, asm.mapping(), stream=stream)
+    pk.permutation = PermutationProvingKey(sigmas, *forms(sigmas))
+    one = _mont_limbs(1, field_modulus(field))
+    ind = np.zeros((3, n, 4), dtype=np.uint64)
+    ind[0, 0] = one                      # l0
+    ind[1, n - bf - 1] = one             # l_last
+    ind[2, :n - bf - 1] = one            # 1 - (l_last + l_blind): l_blind covers the last blinding_factors rows
+    polys, ext_forms = forms(_fixed_values(field, n, list(ind)))
+    pk.l0_poly, pk.l_last_poly, pk.l_active_row_poly = polys[0], polys[1], polys[2]
+    if cosets:
+        pk.l0, pk.l_last, pk.l_active_row = ext_forms[0], ext_forms[1], ext_forms[2]
+    return pk

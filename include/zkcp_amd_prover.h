@@ -171,6 +171,35 @@ int zk_halo2_lookup_product_device(zk_field_t f, const void *a_dev, const void *
  * input, usable_rows >= 2^31.  usable_rows = 0 does nothing.  Scratch: about 160 B per usable row, owned by the stream. */
 int zk_halo2_permute_expression_pair_device(zk_field_t f, const void *inputs_dev, const void *table_dev, uint64_t usable_rows,
                                             void *a_perm_dev, void *s_perm_dev, void *hip_stream);
+/* ---- halo2_proofs 0.2 key generation (plonk/keygen.rs keygen_vk / keygen_pk, plonk/permutation/keygen.rs Assembly) ----
+ * Every transform of the key goes through the NTT entry points of zkcp_amd.h (ZK_NTT_OUT_R29 for the lazy form), every commitment
+ * through zk_msm_batch_device, Assigned fixed columns through zk_batch_invert_device (a zero denominator gives 0, upstream's rule);
+ * what is left is the copy-constraint permutation and its columns.  Circuit synthesis, floor planning, compress_selectors and the
+ * key's transcript representation stay with the caller.
+ *
+ * plonk/permutation/keygen.rs Assembly::new(n, columns): mapping[c][r] = aux[c][r] = (c, r), sizes[c][r] = 1 over ncols columns of
+ * n rows, in host memory (the walk of a cycle is sequential by definition).  ncols x n must stay below 2^32 cells (16 B a cell). */
+int zk_halo2_assembly_new(uint64_t n, uint32_t ncols, uint64_t *handle_out);
+/* Assembly::copy(left_column, left_row, right_column, right_row) for `count` quadruples of quads_host, applied in order: a copy
+ * inside one cycle does nothing; otherwise the larger cycle (the left one on a tie) absorbs the other and mapping[left], mapping[right]
+ * are swapped, so the permutation depends on the order of the calls exactly as upstream's does.  A row >= n or a column >= ncols
+ * (upstream: Error::BoundsFailure) stops the walk with ZK_ERR_INVALID_ARG: the earlier copies stay applied, the rest are not
+ * looked at, and *applied_out (optional) = how many were applied.  ZK_ERR_BAD_HANDLE for an unknown or freed handle. */
+int zk_halo2_assembly_copy(uint64_t handle, const uint32_t *quads_host, uint64_t count, uint64_t *applied_out);
+/* the permutation as it stands: ncols x n words, mapping_out_host[c * n + r] = column << 32 | row of the cell that (c, r) maps to */
+int zk_halo2_assembly_mapping(uint64_t handle, void *mapping_out_host);
+int zk_halo2_assembly_free(uint64_t handle);
+/* Assembly::build_vk / build_pk, the permutation columns in Lagrange form on the 2^k-row domain:
+ *   sigmas_dev[c * n + j] = delta^col * omega^row   for mapping_dev[c * n + j] = col << 32 | row   (upstream: deltaomega[col][row])
+ * delta: FieldExt::DELTA in Montgomery form, host; omega: the domain's generator.  Column c is sigmas_dev + c * n, usable as it is
+ * as a sigmas_dev entry of zk_halo2_permutation_product_device.  The mapping is device data the library did not produce: a cell
+ * whose row >= n or column >= ncols is never used as an index, gets 0 in its own slot, and the call returns ZK_ERR_INVALID_ARG;
+ * the library stays usable.  Also ZK_ERR_INVALID_ARG, before anything is launched: null or misaligned (16 B) pointers, buffers
+ * that overlap, ncols = 0, k above the field's two-adicity, 2^k * ncols >= 2^32.  Synchronises hip_stream once, at the end, to
+ * read the status word. */
+int zk_halo2_permutation_sigmas_device(zk_field_t f, uint32_t k, uint32_t ncols, const void *mapping_dev, const void *delta_mont_host,
+                                       void *sigmas_dev, void *hip_stream);
+
 /* poly/commitment/prover.rs create_proof, the scalar side of one round: compute_inner_product, and the folds
  * p'[i] += u^-1 p'[i + half], b[i] += u b[i + half] as a[i] += c a[i + half] */
 int zk_inner_product_device(zk_field_t f, const void *a_dev, const void *b_dev, uint64_t n, void *out_mont_host, void *hip_stream);

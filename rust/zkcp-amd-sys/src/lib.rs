@@ -250,6 +250,12 @@ extern "C" {
                                           z_last_out_host: *mut c_void, hip_stream: *mut c_void) -> c_int;
     pub fn zk_halo2_permute_expression_pair_device(f: c_int, inputs_dev: *const c_void, table_dev: *const c_void, usable_rows: u64,
                                                    a_perm_dev: *mut c_void, s_perm_dev: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn zk_halo2_assembly_new(n: u64, ncols: u32, handle_out: *mut u64) -> c_int;
+    pub fn zk_halo2_assembly_copy(handle: u64, quads_host: *const u32, count: u64, applied_out: *mut u64) -> c_int;
+    pub fn zk_halo2_assembly_mapping(handle: u64, mapping_out_host: *mut c_void) -> c_int;
+    pub fn zk_halo2_assembly_free(handle: u64) -> c_int;
+    pub fn zk_halo2_permutation_sigmas_device(f: c_int, k: u32, ncols: u32, mapping_dev: *const c_void, delta_mont_host: *const c_void,
+                                              sigmas_dev: *mut c_void, hip_stream: *mut c_void) -> c_int;
     pub fn zk_inner_product_device(f: c_int, a_dev: *const c_void, b_dev: *const c_void, n: u64, out_mont_host: *mut c_void,
                                    hip_stream: *mut c_void) -> c_int;
     pub fn zk_poly_eval_device(f: c_int, coeffs_dev: *const c_void, n: u64, x_mont_host: *const c_void, out_mont_host: *mut c_void,
@@ -451,6 +457,11 @@ impl DeviceBuf {
         assert_eq!(unsafe { hipMemcpy(out.as_mut_ptr() as _, src as _, out.len() * 8, HIP_MEMCPY_DEVICE_TO_HOST) }, 0, "hipMemcpy D2H");
     }
     pub fn ptr(&self) -> *mut c_void { self.ptr }
+    /// the address of word `first_word` (column c of a [count, n, 4] buffer starts at word c * n * 4)
+    pub fn ptr_at(&self, first_word: usize) -> *mut c_void {
+        assert!(first_word <= self.len);
+        unsafe { (self.ptr as *mut u64).add(first_word) as *mut c_void }
+    }
     pub fn len(&self) -> usize { self.len }
 }
 impl Drop for DeviceBuf {
