@@ -4,6 +4,8 @@ include/zkcp_amd_prover.h:
   ark_to_bytes / ark_from_bytes            circuits-ark/src/utils.rs:12-22  (CanonicalSerialize::serialize = compressed)
   ProvingKey.deserialize_unchecked / serialize_unchecked    lib/src/utils.rs:85-110 (the key file `compile` writes, `sell` reads)
   VerifyingKey (compressed)                lib/src/utils.rs:93,112-118
+  points_from_bytes_checked[_device]       CanonicalDeserialize::deserialize of GroupAffine / Vec<GroupAffine> (read_verifying_key):
+                                           canonical coordinates, flags, the curve, the r-order subgroup
   Proof (compressed a, b, c)               lib/src/zk/encryption.rs:80 `ark_to_bytes(proof)`
   VerifiableEncryption JSON                lib/src/zk/verifiable_encryption.rs:23-34, cipher_host.rs:25-42 (serde_json)
 
@@ -14,14 +16,15 @@ import json
 
 import numpy as np
 
-from . import Bases, _check, _np64, _ptr, base_limbs, curve_id, load
+from . import Bases, ZkError, _check, _np64, _ptr, base_limbs, curve_id, load
 
 BN254, BLS12_381 = 0, 1
 PAIRING_NAMES = {"Bn254": BN254, "Bls381": BLS12_381}
 PAIRING_CURVES = {BN254: ("Bn254G1", "Bn254G2"), BLS12_381: ("Bls381G1", "Bls381G2")}
 
 PROVER_EXPORTS = ["zk_ark_point_size", "zk_ark_points_encode", "zk_ark_points_decode", "zk_ark_scalars_encode", "zk_ark_scalars_decode",
-                  "zk_ark_proving_key_index", "zk_bases_upload_ark", "zk_ark_proof_size", "zk_ark_proof_encode", "zk_ark_proof_decode"]
+                  "zk_ark_proving_key_index", "zk_bases_upload_ark", "zk_ark_proof_size", "zk_ark_proof_encode", "zk_ark_proof_decode",
+                  "zk_ark_points_decode_checked", "zk_ark_points_decode_checked_device"]
 
 
 class Span(ctypes.Structure):
@@ -53,6 +56,8 @@ def _lib():
     lib.zk_bases_upload_ark.argtypes = [i32, u8p, u64, ctypes.POINTER(u64)]
     lib.zk_ark_proof_encode.argtypes = [i32, vp, vp, vp, vp]
     lib.zk_ark_proof_decode.argtypes = [i32, u8p, vp, vp, vp]
+    lib.zk_ark_points_decode_checked.argtypes = [i32, u8p, u64, i32, vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.zk_ark_points_decode_checked_device.argtypes = [i32, u8p, u64, i32, vp, ctypes.POINTER(u64), ctypes.POINTER(u64), vp]
     return lib
 
 
@@ -72,6 +77,46 @@ def points_from_bytes(curve, buf, n, compressed=True, check_on_curve=False):
     out = np.zeros((n, 2 * base_limbs(curve)), dtype=np.uint64)
     _check(_lib().zk_ark_points_decode(curve_id(curve), bytes(buf), n, int(compressed), int(check_on_curve), _ptr(out)), "zk_ark_points_decode")
     return out
+
+
+DECODE_REASONS = {1: "non-canonical coordinate", 2: "invalid flags", 3: "not on the curve", 4: "not in the subgroup"}
+
+
+class PointDecodeError(ZkError):
+    """a checked decoder refused the input: `.index` = the first refused point, `.reason` = 1 non-canonical coordinate, 2 flags,
+    3 not on the curve, 4 not in the r-order subgroup (0 when the call was refused for another cause)"""
+
+    def __init__(self, status, what, index, reason):
+        super().__init__(status, what)
+        self.index, self.reason = int(index), int(reason)
+        if reason:
+            self.args = ("%s: point %d, %s" % (self.args[0], self.index, DECODE_REASONS.get(self.reason, "?")),)
+
+
+def points_from_bytes_checked(curve, buf, n, compressed=True):
+    """GroupAffine::deserialize / the checked deserialize_uncompressed for n concatenated points, on the host (G1 and G2 of
+    both pairings) -> [n, 2 * limbs]; raises PointDecodeError"""
+    if len(buf) != n * point_size(curve, compressed):
+        raise ValueError("wrong length for %d points" % n)
+    out = np.zeros((n, 2 * base_limbs(curve)), dtype=np.uint64)
+    idx, why = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    st = _lib().zk_ark_points_decode_checked(curve_id(curve), bytes(buf), n, int(compressed), _ptr(out), ctypes.byref(idx), ctypes.byref(why))
+    if st != 0:
+        raise PointDecodeError(st, "zk_ark_points_decode_checked", idx.value, why.value)
+    return out
+
+
+def points_from_bytes_checked_device(curve, buf, n, d_out, compressed=True, stream=0):
+    """the same decode on the GPU, one lane per point (Bn254G1 / Bls381G1): the encoded bytes (host) -> d_out, a device buffer
+    of [n, 2 * limbs] u64 that a `Bases` can adopt as it is.  Synchronises `stream`; raises PointDecodeError"""
+    if len(buf) != n * point_size(curve, compressed) or int(d_out.shape[0]) < n:
+        raise ValueError("wrong length for %d points" % n)
+    idx, why = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    st = _lib().zk_ark_points_decode_checked_device(curve_id(curve), bytes(buf), n, int(compressed), _ptr(d_out), ctypes.byref(idx),
+                                                    ctypes.byref(why), ctypes.c_void_p(stream))
+    if st != 0:
+        raise PointDecodeError(st, "zk_ark_points_decode_checked_device", idx.value, why.value)
+    return d_out
 
 
 def vec_to_bytes(curve, pts, compressed=True):
@@ -195,6 +240,17 @@ def proof_from_bytes(pairing, buf):
         raise ValueError("wrong proof length")
     _check(_lib().zk_ark_proof_decode(pairing, bytes(buf), _ptr(a), _ptr(b), _ptr(c)), "zk_ark_proof_decode")
     return a, b, c
+
+
+def proof_from_bytes_checked(pairing, buf):
+    """Proof::deserialize: a, b, c through the checked host decoder"""
+    pairing = pairing_id(pairing)
+    g1, g2 = PAIRING_CURVES[pairing]
+    s1, s2 = point_size(g1, True), point_size(g2, True)
+    if len(buf) != 2 * s1 + s2:
+        raise ValueError("wrong proof length")
+    return (points_from_bytes_checked(g1, buf[:s1], 1)[0], points_from_bytes_checked(g2, buf[s1:s1 + s2], 1)[0],
+            points_from_bytes_checked(g1, buf[s1 + s2:], 1)[0])
 
 
 class VerifiableEncryption:

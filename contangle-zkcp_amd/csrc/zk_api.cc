@@ -1722,6 +1722,18 @@ API int zk_ntt_points(zk_curve_t c, void* jac, uint32_t log_n, const void* omega
     });
     return ZK_ERR_INVALID_ARG;
 }
+API int zk_ark_points_decode_checked_device(zk_curve_t c, const uint8_t* in_host, uint64_t n, int compressed, void* out_dev, uint64_t* first_bad_index,
+                                            uint64_t* reason, void* stream) {
+    if (first_bad_index) *first_bad_index = 0;
+    if (reason) *reason = 0;
+    if (c != ZK_BN254_G1 && c != ZK_BLS12_381_G1) return ZK_ERR_UNSUPPORTED;
+    if (n == 0) return ZK_OK;
+    if (!in_host || !out_dev || !aligned16(out_dev)) return ZK_ERR_INVALID_ARG;
+    DEVICE_ENTRY(out_dev);
+    CURVE_SWITCH(c, return points_decode_checked_run<C>(dc, in_host, n, compressed ? 1 : 0, (Affine<C>*)out_dev, first_bad_index, reason,
+                                                       (hipStream_t)stream));
+    return ZK_ERR_INVALID_ARG;
+}
 API int zk_ipa_collapse_device(zk_curve_t c, uint64_t handle, const void* w, uint64_t m0, uint64_t cur, void* g_out, void* stream) {
     return zk_ipa_collapse_range_device(c, handle, w, m0, cur, 0, cur, g_out, stream);
 }
@@ -1881,6 +1893,27 @@ API int zk_point_to_affine(zk_curve_t c, const void* jac, void* aff) {
         Affine<C> r;
         xyzz_to_affine(r, x);
         memcpy(aff, &r, 2 * 4 * coord_words<C>());
+    });
+    return ZK_OK;
+}
+
+API int zk_groth16_prepare_inputs(zk_curve_t g1, uint64_t gamma_abc_tail_bases, const void* gamma_abc0_affine, uint64_t gamma_abc_len,
+                                  const void* inputs_mont_dev, uint64_t n_inputs, void* g_ic_affine_out, void* stream) {
+    if (!gamma_abc0_affine || !g_ic_affine_out || (g1 != ZK_BN254_G1 && g1 != ZK_BLS12_381_G1)) return ZK_ERR_INVALID_ARG;
+    if (n_inputs + 1 != gamma_abc_len) return ZK_ERR_INVALID_ARG;   // upstream: SynthesisError::MalformedVerifyingKey; nothing is launched
+    CURVE_SWITCH(g1, {
+        Jacobian<C> sum;
+        XYZZ<C> acc;
+        xyzz_set_inf(acc);
+        if (n_inputs) {
+            ZK_TRY(zk_msm_device(g1, gamma_abc_tail_bases, inputs_mont_dev, n_inputs, 1, nullptr, &sum, stream));
+            jac_to_xyzz(acc, sum);
+        }
+        Affine<C> first, r;
+        memcpy(&first, gamma_abc0_affine, 2 * 4 * coord_words<C>());
+        xyzz_add_mixed(acc, first);
+        xyzz_to_affine(r, acc);
+        memcpy(g_ic_affine_out, &r, 2 * 4 * coord_words<C>());
     });
     return ZK_OK;
 }

@@ -811,3 +811,4 @@ int ipa_collapse_run(DeviceCtx& dc, const BasesCopy& bc, uint64_t base_n, const 
 }
 }  // namespace zk
 #include "zk_ecfft.inl"
+#include "zk_decode.inl"

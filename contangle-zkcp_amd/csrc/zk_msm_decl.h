@@ -26,4 +26,8 @@ template <class C>
 int ntt_points_run(DeviceCtx& dc, const Affine<C>* src, Affine<C>* dst, uint32_t logn, const Fe<typename C::Fr>& omega_mont, int scale, hipStream_t st);
 template <class C>
 int ntt_points_host_run(DeviceCtx& dc, void* jac_host, uint32_t logn, const Fe<typename C::Fr>& omega_mont, int scale);
+// the checked decode of ark-serialize points (zk_decode_kernels.h): BN254 G1 and BLS12-381 G1, ZK_ERR_UNSUPPORTED elsewhere
+template <class C>
+int points_decode_checked_run(DeviceCtx& dc, const uint8_t* in_host, uint64_t n, int compressed, Affine<C>* d_out, uint64_t* first_bad, uint64_t* reason,
+                              hipStream_t st);
 }  // namespace zk

@@ -12,4 +12,5 @@ template int ipa_collapse_run<ZK_CURVE>(DeviceCtx&, const BasesCopy&, uint64_t, 
                                         hipStream_t);
 template int ntt_points_run<ZK_CURVE>(DeviceCtx&, const Affine<ZK_CURVE>*, Affine<ZK_CURVE>*, uint32_t, const Fe<ZK_CURVE::Fr>&, int, hipStream_t);
 template int ntt_points_host_run<ZK_CURVE>(DeviceCtx&, void*, uint32_t, const Fe<ZK_CURVE::Fr>&, int);
+template int points_decode_checked_run<ZK_CURVE>(DeviceCtx&, const uint8_t*, uint64_t, int, Affine<ZK_CURVE>*, uint64_t*, uint64_t*, hipStream_t);
 }  // namespace zk

@@ -5,6 +5,7 @@
 #include "zk_host64.h"
 #include "zkcp_amd_prover.h"
 
+#include <atomic>
 #include <thread>
 
 using namespace zk;
@@ -337,6 +338,71 @@ void scalar_mul_h(HostXYZZ<C>& r, const HostXYZZ<C>& p, const uint32_t* k, int n
     }
     r = acc;
 }
+// ark-ec 0.3 is_in_correct_subgroup_assuming_on_curve: [r] P == O
+template <class C>
+bool in_subgroup(const Affine<C>& p) {
+    XYZZ<C> x;
+    HostXYZZ<C> h, acc;
+    xyzz_from_affine(x, p);
+    to_host<C>(h, x);
+    scalar_mul_h<C>(acc, h, C::Fr::P, C::Fr::N);
+    from_host<C>(x, acc);
+    return xyzz_is_inf(x);
+}
+// GroupAffine::deserialize / the checked deserialize_uncompressed: 0, or why the point is refused (1 non-canonical coordinate,
+// 2 flags, 3 not on the curve, 4 not in the subgroup)
+template <class C>
+int decode_one_checked(Affine<C>& p, const uint8_t* in, int compressed) {
+    constexpr int CB = coord_bytes<C>();
+    uint8_t flags = 0, none = 0;
+    if (compressed) {
+        if (!get_coord(p.x, in, true, &flags)) return 1;
+    } else {
+        if (!get_coord(p.x, in, false, &none) || !get_coord(p.y, in + CB, true, &flags)) return 1;
+    }
+    if (flags == 0xC0) return 2;
+    if (flags & 0x40) {
+        fe_zero(p.x);
+        fe_zero(p.y);
+        return 0;
+    }
+    if (compressed) {
+        Coord<C> rhs, b, y;
+        fe_sqr(rhs, p.x);
+        fe_mul(rhs, rhs, p.x);
+        curve_b<C>(b);
+        fe_add(rhs, rhs, b);
+        if (!fe_sqrt(y, rhs)) return 3;
+        if (larger_than_neg(y) != ((flags & 0x80) != 0)) fe_neg(y, y);
+        p.y = y;
+    } else if (!on_curve<C>(p)) {
+        return 3;
+    }
+    return in_subgroup<C>(p) ? 0 : 4;
+}
+template <class C>
+int decode_points_checked(const uint8_t* in, uint64_t n, int compressed, void* aff_out, uint64_t* first_bad, uint64_t* reason) {
+    const size_t pb = (size_t)point_bytes<C>(compressed);
+    std::atomic<uint64_t> bad{~0ull};      // index << 3 | reason; every worker stops at the first point it refuses
+    parallel_for(n, [&](uint64_t i) {
+        Affine<C> q;
+        const int why = decode_one_checked<C>(q, in + i * pb, compressed);
+        if (why) {
+            uint64_t w = i << 3 | (uint64_t)why, cur = bad.load();
+            while (w < cur && !bad.compare_exchange_weak(cur, w)) {
+            }
+            return (int)ZK_ERR_INVALID_ARG;
+        }
+        memcpy((unsigned char*)aff_out + i * 2 * 4 * coord_words<C>(), &q, 2 * 4 * coord_words<C>());
+        return (int)ZK_OK;
+    });
+    const uint64_t w = bad.load();
+    if (w == ~0ull) return ZK_OK;
+    if (first_bad) *first_bad = w >> 3;
+    if (reason) *reason = w & 7;
+    return ZK_ERR_INVALID_ARG;
+}
+
 template <class C>
 void store_affine_h(void* out, const HostXYZZ<C>& p) {
     XYZZ<C> x;
@@ -450,6 +516,20 @@ API int zk_ark_points_decode(zk_curve_t c, const uint8_t* in, uint64_t n, int co
         case ZK_BN254_G2: return decode_points<Bn254G2>(in, n, compressed, check, aff_out);
         case ZK_BLS12_381_G1: return decode_points<Bls381G1>(in, n, compressed, check, aff_out);
         case ZK_BLS12_381_G2: return decode_points<Bls381G2>(in, n, compressed, check, aff_out);
+        default: return ZK_ERR_UNSUPPORTED;
+    }
+}
+
+API int zk_ark_points_decode_checked(zk_curve_t c, const uint8_t* in, uint64_t n, int compressed, void* aff_out, uint64_t* first_bad_index,
+                                     uint64_t* reason) {
+    if (first_bad_index) *first_bad_index = 0;
+    if (reason) *reason = 0;
+    if (n && (!in || !aff_out)) return ZK_ERR_INVALID_ARG;
+    switch (c) {
+        case ZK_BN254_G1: return decode_points_checked<Bn254G1>(in, n, compressed, aff_out, first_bad_index, reason);
+        case ZK_BN254_G2: return decode_points_checked<Bn254G2>(in, n, compressed, aff_out, first_bad_index, reason);
+        case ZK_BLS12_381_G1: return decode_points_checked<Bls381G1>(in, n, compressed, aff_out, first_bad_index, reason);
+        case ZK_BLS12_381_G2: return decode_points_checked<Bls381G2>(in, n, compressed, aff_out, first_bad_index, reason);
         default: return ZK_ERR_UNSUPPORTED;
     }
 }

@@ -10,6 +10,10 @@ lib/src/zk/encryption.rs:76, verifiable_encryption.rs:92, sample_entries.rs:86, 
                              matrices (three TRANSPOSED sparse mat-vecs), the key scalars, the fixed-base multiplications;
                              -> Parameters: point vectors on the device, serialize_unchecked() = the key file `compile` writes
   generate_random_parameters the same with the five trapdoor scalars drawn from `secrets`
+  VerifyingKey / verify      verifier.rs (the buyer's side: lib/src/zk/encryption.rs:152, sample_entries.rs:126, property.rs:177 after
+                             read_verifying_key): VerifyingKey.deserialize = the CHECKED decode of the key file, gamma_abc_g1 on the
+                             device (one lane per point: square root, subgroup test) and resident from then on; prepare_inputs = one
+                             MSM over it; prepare_verifying_key / verify_proof_with_prepared_inputs = the pairing check on the host
 
 The blinding scalars r, s are arguments: upstream draws them from the caller's RNG, so a proof is reproducible bit for
 bit only when the unmodified Rust prover drives the FFI (SURVEY 7 "hard parts"); everything before them is deterministic.
@@ -19,17 +23,22 @@ import secrets
 
 import numpy as np
 
-from . import (Bases, _check, _np64, _ptr, ark_serialize, backend_info, base_limbs, field_id, field_modulus, fixed_base_msm_device, load,
+from . import (Bases, _check, _np64, _ptr, ark_serialize, backend_info, base_limbs, curve_id, field_id, field_modulus, fixed_base_msm_device, load,
                msm_submit, vec_op)
 
 PROVER_EXPORTS = ["zk_r1cs_matrix_upload", "zk_r1cs_matrix_free", "zk_r1cs_matvec_device", "zk_groth16_witness_map_r1cs_device",
                   "zk_groth16_assemble_proof", "zk_r1cs_matvec_transposed_device", "zk_lagrange_coefficients_device",
-                  "zk_groth16_qap_at_device", "zk_groth16_key_scalars_device"]
+                  "zk_groth16_qap_at_device", "zk_groth16_key_scalars_device", "zk_pairing_product", "zk_groth16_verify",
+                  "zk_groth16_prepare_inputs"]
 
 
 class Assembly(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "delta_g2", "a_query0", "b_g1_query0",
                                                 "b_g2_query0", "a_acc", "b_g1_acc", "l_acc", "h_acc", "b_g2_acc", "r", "s")]
+
+
+class VkPoints(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2")]
 
 
 def _lib():
@@ -44,6 +53,9 @@ def _lib():
     lib.zk_lagrange_coefficients_device.argtypes = [i32, ctypes.c_uint32, vp, vp, vp, vp]
     lib.zk_groth16_qap_at_device.argtypes = [i32, u64, u64, u64, u64, ctypes.c_uint32, vp, vp, vp, vp, u64, vp, vp]
     lib.zk_groth16_key_scalars_device.argtypes = [i32, vp, vp, vp, u64, u64, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.zk_pairing_product.argtypes = [i32, vp, vp, u64, vp]
+    lib.zk_groth16_verify.argtypes = [i32, ctypes.POINTER(VkPoints), vp, vp, vp, vp, vp, ctypes.POINTER(u64)]
+    lib.zk_groth16_prepare_inputs.argtypes = [i32, u64, vp, u64, vp, u64, vp, vp]
     return lib
 
 
@@ -314,3 +326,118 @@ def generate_random_parameters(pairing, A, B, C, num_inputs, n_vars, g1=None, g2
     ints = [draw() for _ in range(4)] + [tau]
     mont = ark_serialize.scalars_from_bytes(field, b"".join(v.to_bytes(32, "little") for v in ints), 5)
     return generate_parameters(pairing, A, B, C, num_inputs, n_vars, mont[0], mont[1], mont[2], mont[3], mont[4], g1=g1, g2=g2, stream=stream)
+
+
+# ---- verification: ark-groth16 0.3 verifier.rs ----
+class MalformedVerifyingKey(ValueError):
+    """SynthesisError::MalformedVerifyingKey: len(public_inputs) + 1 != len(gamma_abc_g1)"""
+
+
+def pairing_product(pairing, g1_points, g2_points):
+    """final_exponentiation(prod_i miller_loop(g1[i], g2[i])) -> the 12 Fq coefficients (Montgomery limbs) in ark's Fp12 order,
+    [12, limbs]; the points must be in their r-order subgroups; (0, 0) in either slot contributes 1"""
+    pairing = ark_serialize.pairing_id(pairing)
+    c1, c2 = ark_serialize.PAIRING_CURVES[pairing]
+    a, b = _np64(g1_points).reshape(-1, 2 * base_limbs(c1)), _np64(g2_points).reshape(-1, 2 * base_limbs(c2))
+    assert a.shape[0] == b.shape[0]
+    out = np.zeros((12, base_limbs(c1)), dtype=np.uint64)
+    _check(_lib().zk_pairing_product(pairing, _ptr(a), _ptr(b), a.shape[0], _ptr(out)), "zk_pairing_product")
+    return out
+
+
+class VerifyingKey:
+    """ark-groth16 0.3 VerifyingKey<E>: alpha_g1, beta_g2, gamma_g2, delta_g2 as host limbs, gamma_abc_g1 resident on the device
+    ([len, 2 * limbs] u64) with a `Bases` handle over gamma_abc_g1[1..] for prepare_inputs."""
+
+    def __init__(self, pairing, alpha_g1, beta_g2, gamma_g2, delta_g2, d_gamma_abc_g1):
+        self.pairing = ark_serialize.pairing_id(pairing)
+        self.g1, self.g2 = ark_serialize.PAIRING_CURVES[self.pairing]
+        self.alpha_g1, self.beta_g2, self.gamma_g2, self.delta_g2 = (_np64(x).ravel().copy() for x in (alpha_g1, beta_g2, gamma_g2, delta_g2))
+        self.d_gamma_abc_g1 = d_gamma_abc_g1
+        self.n = int(d_gamma_abc_g1.shape[0])
+        if self.n == 0:
+            raise MalformedVerifyingKey("gamma_abc_g1 is empty")
+        self.gamma_abc0 = np.ascontiguousarray(_download(d_gamma_abc_g1[0:1])).ravel().copy()
+        self.tail = Bases(self.g1, device_tensor=d_gamma_abc_g1[1:], n=self.n - 1) if self.n > 1 else None
+
+    @classmethod
+    def deserialize(cls, pairing, buf, stream=0):
+        """CanonicalDeserialize::deserialize of the reference's verifying-key file (lib/src/utils.rs:112-118; compressed):
+        every point is checked (canonical, flags, on the curve, in the subgroup) -- the three G2 members and alpha_g1 by the
+        host decoder, gamma_abc_g1 by the device decoder, whose output stays resident.  Raises ark_serialize.PointDecodeError."""
+        pairing = ark_serialize.pairing_id(pairing)
+        buf = bytes(buf)
+        g1, g2 = ark_serialize.PAIRING_CURVES[pairing]
+        s1, s2 = ark_serialize.point_size(g1, True), ark_serialize.point_size(g2, True)
+        head = s1 + 3 * s2
+        if len(buf) < head + 8:
+            raise ValueError("truncated verifying key")
+        n = int.from_bytes(buf[head:head + 8], "little")
+        if len(buf) != head + 8 + n * s1:
+            raise ValueError("the verifying key's length does not match its gamma_abc_g1 count")
+        alpha = ark_serialize.points_from_bytes_checked(g1, buf[:s1], 1)
+        g2s = ark_serialize.points_from_bytes_checked(g2, buf[s1:head], 3)
+        d_abc = _new_buffer((n, 2 * base_limbs(g1)))
+        ark_serialize.points_from_bytes_checked_device(g1, buf[head + 8:], n, d_abc, compressed=True, stream=stream)
+        return cls(pairing, alpha[0], g2s[0], g2s[1], g2s[2], d_abc)
+
+    @classmethod
+    def from_parameters(cls, params):
+        """pk.vk of a `Parameters`: gamma_abc_g1 is adopted where generate_parameters left it"""
+        return cls(params.pairing, params.points("alpha_g1")[0], params.points("beta_g2")[0], params.points("gamma_g2")[0],
+                   params.points("delta_g2")[0], params.device["gamma_abc_g1"])
+
+    def free(self):
+        if self.tail is not None:
+            self.tail.free()
+            self.tail = None
+
+
+class PreparedVerifyingKey:
+    """ark-groth16 0.3 PreparedVerifyingKey: the key and the cached e(alpha_g1, beta_g2) (the negated G2 members are formed inside
+    zk_groth16_verify)"""
+
+    def __init__(self, vk, alpha_g1_beta_g2):
+        self.vk, self.alpha_g1_beta_g2 = vk, alpha_g1_beta_g2
+
+
+def prepare_verifying_key(vk):
+    return PreparedVerifyingKey(vk, pairing_product(vk.pairing, vk.alpha_g1, vk.beta_g2))
+
+
+def prepare_inputs(pvk, public_inputs, stream=0):
+    """g_ic = gamma_abc_g1[0] + sum_i x_i gamma_abc_g1[i + 1] as an affine point (host limbs).  public_inputs: Fr elements in
+    Montgomery form, [l, 4] -- host limbs (uploaded) or a device buffer.  One MSM over the resident gamma_abc_g1[1..]; a length
+    mismatch raises MalformedVerifyingKey and launches nothing."""
+    vk = pvk.vk
+    d_x = _upload(np.asarray(public_inputs, dtype=np.uint64).reshape(-1, 4)) if isinstance(public_inputs, (np.ndarray, list, tuple)) else public_inputs
+    n_in = int(d_x.shape[0])
+    if n_in + 1 != vk.n:
+        raise MalformedVerifyingKey("%d public inputs for a key with %d gamma_abc_g1 points" % (n_in, vk.n))
+    out = np.zeros(2 * base_limbs(vk.g1), dtype=np.uint64)
+    _check(_lib().zk_groth16_prepare_inputs(curve_id(vk.g1),
+                                            vk.tail.handle if vk.tail is not None else 0, _ptr(vk.gamma_abc0), vk.n,
+                                            _ptr(d_x) if n_in else None, n_in, _ptr(out), ctypes.c_void_p(stream)), "zk_groth16_prepare_inputs")
+    return out
+
+
+def verify_proof_with_prepared_inputs(pvk, proof, g_ic):
+    """e(A, B) e(g_ic, -gamma_g2) e(C, -delta_g2) == e(alpha_g1, beta_g2); proof = (A, B, C) affine limbs -> bool"""
+    vk = pvk.vk
+    a, b, c = (_np64(x).ravel() for x in proof)
+    g_ic = _np64(g_ic).ravel()
+    pts = VkPoints(*[ctypes.cast(_ptr(x), ctypes.c_void_p) for x in (vk.alpha_g1, vk.beta_g2, vk.gamma_g2, vk.delta_g2)])
+    ab = _np64(pvk.alpha_g1_beta_g2)
+    ok = ctypes.c_uint64(0)
+    _check(_lib().zk_groth16_verify(vk.pairing, ctypes.byref(pts), _ptr(ab), _ptr(g_ic), _ptr(a), _ptr(b), _ptr(c), ctypes.byref(ok)),
+           "zk_groth16_verify")
+    return bool(ok.value)
+
+
+def verify(vk, public_inputs, proof, stream=0):
+    """Groth16::verify: vk a VerifyingKey (or a PreparedVerifyingKey, to reuse its cached pairing); proof = (A, B, C) affine limbs or
+    the 192 / 128 bytes of ark_to_bytes(proof), which go through the checked host decoder -> bool"""
+    pvk = vk if isinstance(vk, PreparedVerifyingKey) else prepare_verifying_key(vk)
+    if isinstance(proof, (bytes, bytearray, memoryview)):
+        proof = ark_serialize.proof_from_bytes_checked(pvk.vk.pairing, bytes(proof))
+    return verify_proof_with_prepared_inputs(pvk, proof, prepare_inputs(pvk, public_inputs, stream=stream))

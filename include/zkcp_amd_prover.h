@@ -38,6 +38,24 @@ int zk_ark_point_size(zk_curve_t c, int compressed);
 int zk_ark_points_encode(zk_curve_t c, const void *affine_mont, uint64_t n, int compressed, uint8_t *out);
 int zk_ark_points_decode(zk_curve_t c, const uint8_t *in, uint64_t n, int compressed, int check_on_curve, void *affine_mont_out);
 
+/* The CHECKED decoders: GroupAffine::deserialize (compressed = 1) / the checked deserialize_uncompressed (compressed = 0) of
+ * ark-ec 0.3 -- what CanonicalDeserialize::deserialize runs for every element of a Vec, e.g. read_verifying_key at
+ * lib/src/utils.rs:112-118.  Per point, in this order: canonical coordinates (reason 1), a valid flag pair (2), the infinity
+ * flag (decoded as (0, 0) like zk_ark_points_decode), y recovered by the square root and chosen by the sign flag, or the curve
+ * equation for an uncompressed point (3), and is_in_correct_subgroup_assuming_on_curve, [r] P == O (4).  A refused input returns
+ * ZK_ERR_INVALID_ARG with *first_bad_index = the smallest refused index and *reason as above (both optional, zeroed on entry);
+ * the output rows are then unspecified and the library stays usable.
+ *   zk_ark_points_decode_checked         host memory on both sides; BN254 and BLS12-381, G1 and G2 (ZK_ERR_UNSUPPORTED for the
+ *                                        Pasta curves, which have no arkworks wire format); large vectors use all host threads
+ *   zk_ark_points_decode_checked_device  ZK_BN254_G1 and ZK_BLS12_381_G1: encoded bytes in host memory -> affine Montgomery points
+ *                                        in device memory (16-B aligned, n rows, the layout zk_bases_adopt_device takes), one GPU
+ *                                        lane per point.  One copy to the device, one launch; synchronises hip_stream once, at
+ *                                        the end, to read the status word.  Staging: n encoded points in the stream's scratch. */
+int zk_ark_points_decode_checked(zk_curve_t c, const uint8_t *in, uint64_t n, int compressed, void *affine_mont_out, uint64_t *first_bad_index,
+                                 uint64_t *reason);
+int zk_ark_points_decode_checked_device(zk_curve_t c, const uint8_t *in_host, uint64_t n, int compressed, void *affine_mont_out_dev,
+                                        uint64_t *first_bad_index, uint64_t *reason, void *hip_stream);
+
 /* Fr elements: canonical little-endian 32 bytes (ark-ff 0.3 Fp256::serialize) <-> Montgomery limbs */
 int zk_ark_scalars_encode(zk_field_t f, const void *mont, uint64_t n, uint8_t *out);
 int zk_ark_scalars_decode(zk_field_t f, const uint8_t *in, uint64_t n, void *mont_out);
@@ -99,6 +117,34 @@ typedef struct {
 } zk_groth16_assembly;
 int zk_groth16_assemble_proof(zk_pairing_t p, const zk_groth16_assembly *in, void *a_g1_affine_out, void *b_g2_affine_out,
                               void *c_g1_affine_out);
+
+/* ---- Groth16 verification (ark-groth16 0.3 verifier.rs; the reference's buyer reaches Groth16::verify at
+ * lib/src/zk/encryption.rs:152, sample_entries.rs:126, property.rs:177 after read_verifying_key) ----
+ * prepare_inputs, g_ic = gamma_abc_g1[0] + sum_i x_i gamma_abc_g1[i + 1], is one zk_msm_device over the resident gamma_abc_g1[1..]
+ * (the output of zk_ark_points_decode_checked_device adopted with zk_bases_adopt_device) with scalars_are_montgomery = 1, plus
+ * one zk_point_add; upstream runs a serial loop of scalar multiplications.  What is left is the pairing check, on the host:
+ *
+ * gt_out = final_exponentiation(prod_{i < n} miller_loop(g1[i], g2[i])): the optimal ate pairing, e(P, Q) = f^((p^12 - 1) / r)
+ * exactly, as 12 Fq coefficients in Montgomery limbs in ark's Fp12 order (c0.c0.c0, c0.c0.c1, c0.c1.c0, ... over
+ * Fq2 = Fq[u]/(u^2 + 1), Fq6 = Fq2[v]/(v^3 - xi), Fq12 = Fq6[w]/(w^2 - v); xi = 1 + u on BLS12-381, 9 + u on BN254).
+ * g1 / g2: n affine Montgomery points each; a pair with the identity (0, 0) in either slot contributes 1; n = 0 gives 1.  The
+ * points must lie in their r-order subgroups (the checked decoders above establish that); other input gives an unspecified value. */
+int zk_pairing_product(zk_pairing_t p, const void *g1_affine, const void *g2_affine, uint64_t n, void *gt_out);
+/* verifier.rs prepare_inputs: g_ic = gamma_abc_g1[0] + sum_{i < n_inputs} x_i gamma_abc_g1[i + 1], affine Montgomery, host memory.
+ * gamma_abc_tail_bases: a bases handle over gamma_abc_g1[1..] (gamma_abc_len - 1 points; not looked at when n_inputs = 0);
+ * gamma_abc0_affine: gamma_abc_g1[0], host; inputs_mont_dev: the public inputs as Montgomery Fr elements in device memory.
+ * n_inputs + 1 != gamma_abc_len is upstream's MalformedVerifyingKey: ZK_ERR_INVALID_ARG, and nothing is launched.
+ * One zk_msm_device (scalars_are_montgomery = 1) on hip_stream and one host addition. */
+int zk_groth16_prepare_inputs(zk_curve_t g1, uint64_t gamma_abc_tail_bases, const void *gamma_abc0_affine, uint64_t gamma_abc_len,
+                              const void *inputs_mont_dev, uint64_t n_inputs, void *g_ic_affine_out, void *hip_stream);
+/* verify_proof_with_prepared_inputs: *ok = (e(A, B) e(g_ic, -gamma_g2) e(C, -delta_g2) == e(alpha_g1, beta_g2)).
+ * alpha_g1_beta_g2: the right-hand side as zk_pairing_product writes it (PreparedVerifyingKey caches it), NULL = compute it.
+ * prepared_inputs_g1 = g_ic, affine.  A false proof gives *ok = 0 and returns ZK_OK; errors are for malformed arguments. */
+typedef struct {
+    const void *alpha_g1, *beta_g2, *gamma_g2, *delta_g2;
+} zk_groth16_vk_points;
+int zk_groth16_verify(zk_pairing_t p, const zk_groth16_vk_points *vk, const void *alpha_g1_beta_g2, const void *prepared_inputs_g1,
+                      const void *a_g1, const void *b_g2, const void *c_g1, uint64_t *ok);
 
 /* ---- Groth16 key generation (ark-groth16 0.3 generator.rs generate_parameters; the reference's `compile` reaches it through
  * Groth16::setup at lib/src/zk/encryption.rs:169, sample_entries.rs:141, property.rs:192) ----

@@ -113,6 +113,15 @@ pub struct zk_ark_pk_index {
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct zk_groth16_vk_points {
+    pub alpha_g1: *const c_void,
+    pub beta_g2: *const c_void,
+    pub gamma_g2: *const c_void,
+    pub delta_g2: *const c_void,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct zk_groth16_assembly {
     pub alpha_g1: *const c_void,
     pub beta_g1: *const c_void,
@@ -218,6 +227,16 @@ extern "C" {
                                c_g1_affine_mont: *const c_void, out: *mut u8) -> c_int;
     pub fn zk_ark_proof_decode(p: c_int, input: *const u8, a_g1_affine_mont: *mut c_void, b_g2_affine_mont: *mut c_void,
                                c_g1_affine_mont: *mut c_void) -> c_int;
+    pub fn zk_ark_points_decode_checked(c: c_int, input: *const u8, n: u64, compressed: c_int, affine_mont_out: *mut c_void,
+                                        first_bad_index: *mut u64, reason: *mut u64) -> c_int;
+    pub fn zk_ark_points_decode_checked_device(c: c_int, in_host: *const u8, n: u64, compressed: c_int, affine_mont_out_dev: *mut c_void,
+                                               first_bad_index: *mut u64, reason: *mut u64, hip_stream: *mut c_void) -> c_int;
+    pub fn zk_pairing_product(p: c_int, g1_affine: *const c_void, g2_affine: *const c_void, n: u64, gt_out: *mut c_void) -> c_int;
+    pub fn zk_groth16_prepare_inputs(g1: c_int, gamma_abc_tail_bases: u64, gamma_abc0_affine: *const c_void, gamma_abc_len: u64,
+                                     inputs_mont_dev: *const c_void, n_inputs: u64, g_ic_affine_out: *mut c_void,
+                                     hip_stream: *mut c_void) -> c_int;
+    pub fn zk_groth16_verify(p: c_int, vk: *const zk_groth16_vk_points, alpha_g1_beta_g2: *const c_void, prepared_inputs_g1: *const c_void,
+                             a_g1: *const c_void, b_g2: *const c_void, c_g1: *const c_void, ok: *mut u64) -> c_int;
     pub fn zk_r1cs_matrix_upload(f: c_int, row_ptr_host: *const u64, col_idx_host: *const u32, val_mont_host: *const c_void, n_rows: u64,
                                  n_cols: u64, handle_out: *mut u64) -> c_int;
     pub fn zk_r1cs_matrix_free(handle: u64) -> c_int;
