@@ -1803,6 +1803,37 @@ API int zk_ipa_update_weights_device(zk_field_t f, void* w, uint64_t m0, uint64_
     });
     return ZK_ERR_INVALID_ARG;
 }
+// ---- halo2 opening verification: poly/commitment/verifier.rs compute_s on the device (zk_ipa_verify.inl), compute_b on host limbs
+API int zk_halo2_ipa_s_device(zk_field_t f, uint32_t k, uint32_t count, const void* u_host, const void* init_host, void* s_dev, int accumulate,
+                              void* stream) {
+    if (!u_host || !init_host || !s_dev || !aligned16(u_host) || !aligned16(init_host) || !aligned16(s_dev) || count == 0 || k == 0)
+        return ZK_ERR_INVALID_ARG;
+    FIELD_SWITCH(f, {
+        if (k > (uint32_t)F::TWO_ADICITY) return ZK_ERR_INVALID_ARG;
+    });
+    DEVICE_ENTRY(s_dev);
+    FIELD_SWITCH(f, return ipa_s_run<F>(dc, k, count, u_host, init_host, (Fe<F>*)s_dev, accumulate, (hipStream_t)stream));
+    return ZK_ERR_INVALID_ARG;
+}
+API int zk_halo2_ipa_compute_b(zk_field_t f, uint32_t k, const void* x, const void* u_host, void* out) {
+    if (!x || !u_host || !out || k == 0) return ZK_ERR_INVALID_ARG;
+    FIELD_SWITCH(f, {
+        if (k > (uint32_t)F::TWO_ADICITY) return ZK_ERR_INVALID_ARG;
+        Fe<F> cur, acc, one, t;
+        host_load(cur, x);
+        fe_one(one);
+        acc = one;
+        for (uint32_t j = k; j-- > 0;) {      // the last round's challenge goes with x^1: cur = x^(2^(k - 1 - j))
+            host_load(t, (const unsigned char*)u_host + (size_t)j * sizeof(Fe<F>));
+            fe_mul(t, t, cur);
+            fe_add(t, t, one);
+            fe_mul(acc, acc, t);
+            fe_sqr(cur, cur);
+        }
+        host_store(out, acc);
+    });
+    return ZK_OK;
+}
 API int zk_expr_eval_device(zk_field_t f, const zk_expr_op* prog, uint32_t n_ops, const void* const* cols, uint32_t n_cols, const void* consts,
                             uint32_t n_consts, uint32_t log_n, uint32_t rot_scale, void* out, void* stream) {
     if (!prog || !out || !aligned16(out) || (n_cols && !cols) || (n_consts && !consts)) return ZK_ERR_INVALID_ARG;

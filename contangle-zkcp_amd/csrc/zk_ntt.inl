@@ -363,3 +363,4 @@ int witness_map_run(DeviceCtx& dc, int field, Fe<F>* a, Fe<F>* b, Fe<F>* c, uint
 #include "zk_lookup.inl"
 #include "zk_setup.inl"
 #include "zk_keygen.inl"
+#include "zk_ipa_verify.inl"

@@ -43,4 +43,5 @@ template int groth16_key_scalars_run<ZK_FIELD>(DeviceCtx&, const Fe<ZK_FIELD>*, 
                                                const Fe<ZK_FIELD>&, Fe<ZK_FIELD>*, Fe<ZK_FIELD>*, hipStream_t);
 template int perm_sigmas_run<ZK_FIELD>(DeviceCtx&, int, uint32_t, uint32_t, const uint64_t*, const Fe<ZK_FIELD>&, const Fe<ZK_FIELD>&, Fe<ZK_FIELD>*, int*,
                                        hipStream_t);
+template int ipa_s_run<ZK_FIELD>(DeviceCtx&, uint32_t, uint32_t, const void*, const void*, Fe<ZK_FIELD>*, int, hipStream_t);
 }  // namespace zk

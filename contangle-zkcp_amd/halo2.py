@@ -23,7 +23,7 @@ PROVER_EXPORTS = ["zk_batch_invert_device", "zk_prefix_product_device", "zk_halo
                   "zk_poly_eval_device", "zk_poly_eval_batch_device", "zk_vec_muladd_device", "zk_vec_muladd_to_device", "zk_kate_division_device", "zk_vec_powers_device", "zk_vec_fold_many_device",
                   "zk_ipa_fold_round_device", "zk_expr_eval_lazy_device", "zk_expr_configure", "zk_expr_specialised_source",
                   "zk_halo2_assembly_new", "zk_halo2_assembly_copy", "zk_halo2_assembly_mapping", "zk_halo2_assembly_free",
-                  "zk_halo2_permutation_sigmas_device"]
+                  "zk_halo2_permutation_sigmas_device", "zk_halo2_ipa_s_device", "zk_halo2_ipa_compute_b"]
 
 
 def best_multiexp(coeffs, bases):
@@ -61,16 +61,19 @@ class Params:
     bases.  `from_g` does what Params::new does after it has hashed g: g_lagrange = best_fft(g, omega_k^-1) times n^-1,
     normalised, i.e. g_lagrange[i] = [1/n] sum_j [omega^(-ij)] g_j, the key for which commit_lagrange(evals) ==
     commit(coeffs).  Generating g itself (hash_to_curve("Halo2-Parameters"): BLAKE2b, simplified SWU, isogeny) is not done
-    here and stays with the caller, and so do w and u."""
+    here and stays with the caller, and so do w and u: the caller hands them in (affine Montgomery host points) when it
+    verifies openings (MSM.eval needs both); committing and key generation never look at them."""
 
-    def __init__(self, curve, k, d_g, d_g_lagrange):
+    def __init__(self, curve, k, d_g, d_g_lagrange, u=None, w=None):
         self.curve, self.k, self.n = curve_id(curve), int(k), 1 << int(k)
+        self.u = None if u is None else _np64(u).copy()
+        self.w = None if w is None else _np64(w).copy()
         self.d_g, self.d_g_lagrange = d_g, d_g_lagrange
         self.g = Bases(curve, device_tensor=d_g, n=self.n)                    # zk_bases_adopt_device: no copy
         self.g_lagrange = Bases(curve, device_tensor=d_g_lagrange, n=self.n)
 
     @classmethod
-    def from_g(cls, curve, k, g, stream=0):
+    def from_g(cls, curve, k, g, stream=0, u=None, w=None):
         """g: 2^k affine points (Montgomery u64 limbs [n, 8], identity = (0, 0)), a host array or a device tensor"""
         from .groth16 import _new_buffer, _synchronize, _upload
         n = 1 << int(k)
@@ -82,7 +85,7 @@ class Params:
         d_gl = _new_buffer(tuple(d_g.shape))
         ntt_points_device(curve, d_g, d_gl, int(k), omega_inv, True, stream)
         _synchronize()          # the adopted vectors are read by MSMs on any stream
-        return cls(curve, k, d_g, d_gl)
+        return cls(curve, k, d_g, d_gl, u=u, w=w)
 
     def commit(self, coeffs):
         """commit(poly) without blinding: best_multiexp(coeffs, g); coeffs Montgomery, host or device"""
@@ -355,6 +358,8 @@ def _plib():
     lib.zk_halo2_assembly_mapping.argtypes = [u64, vp]
     lib.zk_halo2_assembly_free.argtypes = [u64]
     lib.zk_halo2_permutation_sigmas_device.argtypes = [i32, u32, u32, vp, vp, vp, vp]
+    lib.zk_halo2_ipa_s_device.argtypes = [i32, u32, u32, vp, vp, vp, i32, vp]
+    lib.zk_halo2_ipa_compute_b.argtypes = [i32, u32, vp, vp, vp]
     return lib
 
 
@@ -993,3 +998,255 @@ def keygen_pk(params, vk, fixed, asm, cosets="mont", stream=0):
     if cosets:
         pk.l0, pk.l_last, pk.l_active_row = ext_forms[0], ext_forms[1], ext_forms[2]
     return pk
+
+
+# ------------------------------------------------------------------ verification (poly/commitment/verifier.rs, poly/commitment/msm.rs)
+IPA_S_MAX_COUNT = 8            # csrc/zk_ipa_verify_kernels.h: proofs per pass of zk_halo2_ipa_s_device (a larger count is chunked inside)
+
+
+def _aligned16(a):
+    """the array as contiguous uint64 limbs at a 16-byte aligned address (the host pointers of zk_halo2_ipa_s_device)"""
+    a = _np64(a)
+    if a.ctypes.data % 16 == 0:
+        return a
+    buf = np.empty(a.size + 2, dtype=np.uint64)
+    off = (-buf.ctypes.data % 16) // 8
+    out = buf[off:off + a.size].reshape(a.shape)
+    out[...] = a
+    return out
+
+
+def _to_int(limbs, p):
+    """Montgomery limbs -> the canonical Python integer"""
+    return sum(int(w) << (64 * i) for i, w in enumerate(_np64(limbs).reshape(-1).tolist())) * pow(1 << 256, -1, p) % p
+
+
+def compute_s(field, u, init, out=None, accumulate=False, stream=0):
+    """verifier.rs compute_s for a batch (zk_halo2_ipa_s_device): out[i] (= or +=) sum_p init[p] prod_j u[p][j]^bit_(k-1-j)(i).
+    u: [count, k, 4] (or [k, 4]) Montgomery host limbs, u[p][0] the first round's challenge; init: [count, 4] (or [4]).
+    out: device buffer [2^k, 4], allocated (and then written, not accumulated into) when None.  One pass over `out`."""
+    from .groth16 import _new_buffer
+    uu = _np64(u)
+    uu = uu.reshape(1, -1, 4) if uu.ndim == 2 else uu
+    ii = _np64(init).reshape(-1, 4)
+    count, k = int(uu.shape[0]), int(uu.shape[1])
+    if int(ii.shape[0]) != count:
+        raise ZkError(ZK_ERR_INVALID_ARG, "compute_s: one init per proof")
+    if out is None:
+        if not 0 < k <= 32:
+            raise ZkError(ZK_ERR_INVALID_ARG, "compute_s: k")
+        out, accumulate = _new_buffer((1 << k, 4)), False
+    elif int(out.shape[0]) != 1 << k:
+        raise AssertionError("assertion failed: s.len() == 1 << k")
+    uu, ii = _aligned16(uu), _aligned16(ii)
+    _check(_plib().zk_halo2_ipa_s_device(field_id(field), k, count, _ptr(uu), _ptr(ii), _ptr(out), int(bool(accumulate)), ctypes.c_void_p(stream)),
+           "zk_halo2_ipa_s_device")
+    return out
+
+
+def compute_b(field, x, u):
+    """verifier.rs compute_b(x, u) = prod_j (1 + u_j x^(2^(k-1-j))) on host limbs (zk_halo2_ipa_compute_b); u: [k, 4]"""
+    uu, xx = _np64(u).reshape(-1, 4), _np64(x)
+    out = np.zeros(4, dtype=np.uint64)
+    _check(_plib().zk_halo2_ipa_compute_b(field_id(field), int(uu.shape[0]), _ptr(xx), _ptr(uu), _ptr(out)), "zk_halo2_ipa_compute_b")
+    return out
+
+
+class MSM:
+    """poly/commitment/msm.rs MSM<C>: a multi-scalar multiplication that is still being put together.  g_scalars lives on the
+    device ([n, 4] Montgomery, None until first needed, upstream's Option) because the opening check adds n scalars to it and
+    the SRS it multiplies is resident; w_scalar, u_scalar (None = upstream's None) and the listed terms are a handful of host
+    values, kept as Python integers.  Scalars come in as Montgomery limbs, points as affine Montgomery host limbs."""
+
+    def __init__(self, params, stream=0):
+        self.params, self.stream = params, stream
+        self.field = scalar_field(params.curve)
+        self.p = field_modulus(self.field)
+        self.g_scalars = None
+        self.w_scalar = self.u_scalar = None
+        self.other_scalars, self.other_bases = [], []
+
+    def _g(self):
+        if self.g_scalars is None:
+            from .groth16 import _new_buffer
+            self.g_scalars = _new_buffer((self.params.n, 4))
+        return self.g_scalars
+
+    def _int(self, s):
+        return s % self.p if isinstance(s, int) else _to_int(s, self.p)
+
+    def append_term(self, scalar, point):
+        self.other_scalars.append(self._int(scalar))
+        self.other_bases.append(_np64(point).copy())
+
+    def add_constant_term(self, constant):
+        """g_scalars[0] += constant: a one-element zk_vec_op_device on the head of the resident vector"""
+        from .groth16 import _upload
+        c = _mont_limbs(self._int(constant), self.p).reshape(1, 4)
+        vec_op(self.field, "add", self._g()[:1], b=_upload(c), stream=self.stream)
+
+    def add_to_g_scalars(self, scalars):
+        """scalars: device buffer [n, 4]"""
+        if int(scalars.shape[0]) != self.params.n:
+            raise AssertionError("assertion failed: scalars.len() == self.params.n")
+        vec_op(self.field, "add", self._g(), b=scalars, stream=self.stream)
+
+    def add_to_w_scalar(self, scalar):
+        self.w_scalar = ((self.w_scalar or 0) + self._int(scalar)) % self.p
+
+    def add_to_u_scalar(self, scalar):
+        self.u_scalar = ((self.u_scalar or 0) + self._int(scalar)) % self.p
+
+    def scale(self, factor):
+        f = self._int(factor)
+        if self.g_scalars is not None:
+            vec_op(self.field, "scale", self.g_scalars, scalar=_mont_limbs(f, self.p), stream=self.stream)
+        self.other_scalars = [s * f % self.p for s in self.other_scalars]
+        if self.w_scalar is not None:
+            self.w_scalar = self.w_scalar * f % self.p
+        if self.u_scalar is not None:
+            self.u_scalar = self.u_scalar * f % self.p
+
+    def add_msm(self, other):
+        self.other_scalars += other.other_scalars
+        self.other_bases += [b.copy() for b in other.other_bases]
+        if other.g_scalars is not None:
+            self.add_to_g_scalars(other.g_scalars)
+        if other.w_scalar is not None:
+            self.add_to_w_scalar(other.w_scalar)
+        if other.u_scalar is not None:
+            self.add_to_u_scalar(other.u_scalar)
+
+    def eval(self):
+        """true when sum other + [w_scalar] W + [u_scalar] U + sum_i [g_scalars[i]] G_i is the identity: ONE zk_msm_device over
+        params.g with the resident g_scalars, one small host-scalar MSM over the listed terms, U and W, and the sum and the
+        identity test on host limbs"""
+        from . import point_add, point_to_affine
+        scalars, bases = list(self.other_scalars), list(self.other_bases)
+        for s, pt, name in ((self.w_scalar, self.params.w, "w"), (self.u_scalar, self.params.u, "u")):
+            if s is not None:
+                if pt is None:
+                    raise ZkError(ZK_ERR_INVALID_ARG, "MSM.eval: the params carry no %s" % name)
+                scalars.append(s)
+                bases.append(pt)
+        nl = load().zk_curve_base_limbs64(self.params.curve)
+        acc = np.zeros(3 * nl, dtype=np.uint64)                    # z = 0: the identity
+        if self.g_scalars is not None:
+            acc = msm(self.params.g, self.g_scalars, montgomery=True, stream=self.stream)
+        if scalars:
+            small = Bases(self.params.curve, np.stack(bases))
+            try:
+                part = msm(small, np.stack([_mont_limbs(s, self.p) for s in scalars]), montgomery=True)
+            finally:
+                small.free()
+            acc = point_add(self.params.curve, acc, part)
+        return not point_to_affine(self.params.curve, acc).any()
+
+
+class IpaProof:
+    """the opening proof in transcript order: S, then xi, z, then (L_j, R_j, u_j) for each of the k rounds, then c, f.  Points
+    are affine Montgomery host limbs, scalars Montgomery limbs; the challenges are the ones the caller's transcript squeezed."""
+
+    def __init__(self, s_commitment, xi, z, rounds, c, f):
+        self.s_commitment, self.xi, self.z, self.rounds, self.c, self.f = s_commitment, xi, z, list(rounds), c, f
+
+
+class Accumulator:
+    """verifier.rs Accumulator: the claimed folded generator g and the challenges that a later compute_g must reproduce"""
+
+    def __init__(self, g, challenges_packed):
+        self.g, self.challenges_packed = g, challenges_packed
+
+
+class Guard:
+    """verifier.rs Guard: the verifier's state before the one linear-time step, which is either done here (use_challenges) or
+    deferred behind a claimed g (use_g; compute_g is what checks such a claim later)"""
+
+    def __init__(self, msm_, neg_c, challenges):
+        self.msm, self.neg_c, self.challenges = msm_, neg_c, challenges      # neg_c: Python integer; challenges: [k, 4] Montgomery
+
+    def use_challenges(self):
+        """msm.add_to_g_scalars(compute_s(u, neg_c)), fused: the kernel adds into the resident g_scalars in its one pass"""
+        m = self.msm
+        fresh = m.g_scalars is None
+        compute_s(m.field, self.challenges, _mont_limbs(self.neg_c, m.p), out=m._g(), accumulate=not fresh, stream=m.stream)
+        return m
+
+    def use_g(self, g):
+        self.msm.append_term(self.neg_c, g)
+        return self.msm, Accumulator(_np64(g).copy(), self.challenges)
+
+    def compute_g(self):
+        """best_multiexp(compute_s(u, 1), params.g) as an affine point"""
+        from . import point_to_affine
+        m = self.msm
+        s = compute_s(m.field, self.challenges, _mont_limbs(1, m.p), stream=m.stream)
+        return point_to_affine(m.params.curve, msm(m.params.g, s, montgomery=True, stream=m.stream))
+
+
+def _proof_challenges(params, msm_, proof):
+    """-> (u as integers, u as [k, 4] limbs); the round count and u_j != 0 checked"""
+    if len(proof.rounds) != params.k:
+        raise ZkError(ZK_ERR_INVALID_ARG, "verify_proof: %d rounds for k = %d" % (len(proof.rounds), params.k))
+    limbs = np.stack([_np64(r[2]) for r in proof.rounds])
+    ints = [_to_int(r[2], msm_.p) for r in proof.rounds]
+    if not all(ints):
+        raise ZkError(ZK_ERR_INVALID_ARG, "verify_proof: a zero challenge has no inverse")
+    return ints, limbs
+
+
+def _append_proof_terms(params, msm_, proof, x, v, weight=1):
+    """steps 1-5 of verify_proof on the host scalars, every scalar times `weight` (an integer); the constant term -v * weight is
+    RETURNED, not applied -> (constant, neg_c * weight, challenges [k, 4])"""
+    p = msm_.p
+    ints, limbs = _proof_challenges(params, msm_, proof)
+    msm_.append_term(weight * _to_int(proof.xi, p), proof.s_commitment)
+    for (l, r, _), uj in zip(proof.rounds, ints):
+        msm_.append_term(weight * pow(uj, -1, p), l)
+        msm_.append_term(weight * uj, r)
+    c, b = _to_int(proof.c, p), _to_int(compute_b(msm_.field, x, limbs), p)
+    msm_.add_to_u_scalar(-c * b * _to_int(proof.z, p) * weight)
+    msm_.add_to_w_scalar(-_to_int(proof.f, p) * weight)
+    return -_to_int(v, p) * weight % p, -c * weight % p, limbs
+
+
+def commitment_verify_proof(params, msm_, proof, x, v):
+    """poly/commitment/verifier.rs verify_proof(params, msm, proof, x, v) -> Guard, for an msm into which the caller has put the
+    commitment being opened (append_term(1, P)).  The transcript stays with the caller: `proof` (IpaProof, or anything with its
+    attributes) carries the points and scalars read from it and the challenges squeezed from it.
+    Deviation from upstream: a challenge u_j = 0 raises ZkError(ZK_ERR_INVALID_ARG) -- upstream's batch_invert leaves the zero
+    in place as its own 'inverse' and goes on; a transcript hash yields 0 with probability 2^-255, so no honest proof is refused.
+    len(proof.rounds) != params.k raises ZkError too.  Both are raised before the msm is touched."""
+    constant, neg_c, limbs = _append_proof_terms(params, msm_, proof, x, v)
+    msm_.add_constant_term(constant)
+    return Guard(msm_, neg_c, limbs)
+
+
+def batch_msm(params, items, weights, stream=0):
+    """the MSM of the batching strategy (halo2's BatchVerifier) over items = [(commitment P, proof, x, v)]: what
+        for item, r in zip(items, weights): msm.scale(r); msm.append_term(1, P); msm = verify_proof(..).use_challenges()
+    leaves, with the g_scalars work fused: proof p's scalars are scaled on the host by t_p = prod_{q > p} r_q, and ONE
+    zk_halo2_ipa_s_device call of count = len(items) with init_p = -c_p t_p writes the whole vector in one pass (upstream and the
+    loop above: k doubling passes plus a scale pass per proof)."""
+    if len(items) != len(weights) or not items:
+        raise ZkError(ZK_ERR_INVALID_ARG, "verify_batch: one weight per item, at least one item")
+    m = MSM(params, stream=stream)
+    tails = [1] * len(items)
+    for q in range(len(items) - 2, -1, -1):
+        tails[q] = tails[q + 1] * _to_int(weights[q + 1], m.p) % m.p
+    constant, inits, challenges = 0, [], []
+    for (commitment, proof, x, v), t in zip(items, tails):
+        m.append_term(t, commitment)
+        c0, neg_c, limbs = _append_proof_terms(params, m, proof, x, v, weight=t)
+        constant = (constant + c0) % m.p
+        inits.append(_mont_limbs(neg_c, m.p))
+        challenges.append(limbs)
+    compute_s(m.field, np.stack(challenges), np.stack(inits), out=m._g(), accumulate=False, stream=stream)
+    m.add_constant_term(constant)
+    return m
+
+
+def verify_batch(params, items, weights, stream=0):
+    """true when every opening of the batch verifies (up to the soundness of the random weights): batch_msm(..).eval() -- one
+    pass for all the g_scalars, one n-point MSM"""
+    return batch_msm(params, items, weights, stream=stream).eval()

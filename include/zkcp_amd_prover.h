@@ -310,6 +310,29 @@ int zk_ipa_collapse_device(zk_curve_t c, uint64_t bases_handle, const void *w_de
 int zk_ipa_collapse_range_device(zk_curve_t c, uint64_t bases_handle, const void *w_dev, uint64_t m0, uint64_t cur, uint64_t first,
                                  uint64_t count, void *g_out_range_dev, void *hip_stream);
 
+/* ---- halo2 verification (halo2_proofs 0.2 poly/commitment/verifier.rs verify_proof / Guard, poly/commitment/msm.rs MSM) ----
+ * The opening check ends in ONE multi-scalar multiplication over the whole SRS, whose scalars are compute_s of the k round
+ * challenges.  That vector is built here; the MSM is zk_msm_device over the resident g with scalars_are_montgomery = 1, the few
+ * listed terms (S, L_j, R_j, U, W) are one small zk_msm, the partial sums meet in zk_point_add and the identity test is
+ * zk_point_to_affine == (0, 0).  The MSM / Guard bookkeeping is contangle-zkcp_amd/halo2.py (MSM, commitment_verify_proof, Guard,
+ * verify_batch); the transcript stays with the caller.
+ *
+ * verifier.rs compute_s(u, init), for `count` proofs in one pass over the vector (Guard::use_challenges adds compute_s(u, neg_c)
+ * to MSM::g_scalars; with many proofs behind one MSM -- the BatchVerifier strategy -- every proof adds its own):
+ *   s_dev[i] (= or +=, by `accumulate`) sum_{p < count} init_p * prod_{j < k} u_{p,j}^bit_(k-1-j)(i),   i < 2^k
+ * u_mont_host: count x k elements, proof-major, u_{p,0} (the first round's challenge, the top bit of i) first; init_mont_host: count
+ * elements; both host memory, 16-B aligned, read before the call returns.  s_dev: 2^k elements, device, 16-B aligned; each is
+ * written once, and read once only when accumulating.  With init = 1 this is the final weight vector of the fold-free prover
+ * (k calls of zk_ipa_update_weights_device on a vector of ones).  A zero challenge is just a product.  Up to 8 proofs share one
+ * pass; a larger count is chunked inside, later chunks accumulating.  Scratch, owned by the stream: 32 B x (2^min(k, 8) +
+ * 2^(k - min(k, 8))) per proof of a chunk.  Does not synchronise hip_stream.  ZK_ERR_INVALID_ARG, before anything is launched: a
+ * null or misaligned (16 B) pointer, count = 0, k = 0, k above the field's two-adicity. */
+int zk_halo2_ipa_s_device(zk_field_t f, uint32_t k, uint32_t count, const void *u_mont_host, const void *init_mont_host, void *s_dev,
+                          int accumulate, void *hip_stream);
+/* verifier.rs compute_b(x, u) = prod_{j < k} (1 + u_j x^(2^(k-1-j))) = sum_i compute_s(u, 1)[i] x^i: k products on host limbs
+ * (Montgomery in and out).  ZK_ERR_INVALID_ARG: a null pointer, k = 0, k above the field's two-adicity. */
+int zk_halo2_ipa_compute_b(zk_field_t f, uint32_t k, const void *x_mont_host, const void *u_mont_host, void *out_mont_host);
+
 /* The quotient numerator: one stack program evaluated at every row of the extended domain (plonk/prover.rs: each gate's
  * Expression over advice / fixed / instance columns with rotations, folded with y).  A rotation by r rows is a shift of
  * r * rot_scale positions (rot_scale = 2^(extended_k - k)), cyclic.  The program must leave exactly one value; it is

@@ -295,6 +295,9 @@ extern "C" {
     pub fn zk_ipa_virtual_scalars_device(f: c_int, p_dev: *const c_void, w_dev: *const c_void, m0: u64, cur: u64, sl_dev: *mut c_void,
                                          sr_dev: *mut c_void, hip_stream: *mut c_void) -> c_int;
     pub fn zk_ipa_update_weights_device(f: c_int, w_dev: *mut c_void, m0: u64, bit: u64, u_mont_host: *const c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn zk_halo2_ipa_s_device(f: c_int, k: u32, count: u32, u_mont_host: *const c_void, init_mont_host: *const c_void, s_dev: *mut c_void,
+                                 accumulate: c_int, hip_stream: *mut c_void) -> c_int;
+    pub fn zk_halo2_ipa_compute_b(f: c_int, k: u32, x_mont_host: *const c_void, u_mont_host: *const c_void, out_mont_host: *mut c_void) -> c_int;
     pub fn zk_ipa_collapse_range_device(c: c_int, bases_handle: u64, w_dev: *const c_void, m0: u64, cur: u64, first: u64, count: u64,
                                         g_out_range_dev: *mut c_void, hip_stream: *mut c_void) -> c_int;
     pub fn zk_ipa_round_device(c: c_int, bases_handle: u64, p_dev: *const c_void, b_dev: *const c_void, w_dev: *const c_void, m0: u64, cur: u64,
