@@ -87,11 +87,18 @@ int zk_ark_proof_decode(zk_pairing_t p, const uint8_t *in, void *a_g1_affine_mon
  *
  * R1CS matrices (ark-relations 0.3 ConstraintMatrices { a, b, c }: one Vec<(coeff, variable index)> per constraint) are
  * fixed per circuit like the proving key: uploaded once in CSR form (row_ptr: n_rows + 1 offsets; col_idx / val per term,
- * val in Montgomery form), resident on the home device. */
+ * val in Montgomery form), resident on the home device.
+ *   Rows: a row may have no term (row_ptr[i + 1] == row_ptr[i]; its product is 0), n_rows may be 0 (row_ptr = {0}) and so may
+ *   the number of terms (col_idx_host / val_mont_host are then not read).  Terms need not be sorted by column, and a column may
+ *   occur more than once in a row: like upstream's evaluate_constraint the products sum every term, so duplicates add up.  A
+ *   coefficient of 0 is an ordinary term.
+ *   Refused with ZK_ERR_INVALID_ARG: row_ptr[0] != 0, a decreasing row_ptr, a col_idx >= n_cols, n_cols >= 2^32. */
 int zk_r1cs_matrix_upload(zk_field_t f, const uint64_t *row_ptr_host, const uint32_t *col_idx_host, const void *val_mont_host,
                           uint64_t n_rows, uint64_t n_cols, uint64_t *handle_out);
 int zk_r1cs_matrix_free(uint64_t handle);
-/* out[i] = <row i, z> for i < n_rows, 0 for n_rows <= i < out_len  (upstream: evaluate_constraint per row) */
+/* out[i] = <row i, z> for i < n_rows, 0 for n_rows <= i < out_len  (upstream: evaluate_constraint per row).  z holds n_cols
+ * elements.  out_len >= n_rows, else ZK_ERR_INVALID_ARG and nothing is written; every one of the out_len elements is written
+ * (the caller's buffer need not be cleared), so out_len = the domain size gives the zero-padded evaluation vector directly. */
 int zk_r1cs_matvec_device(uint64_t matrix, const void *z_mont_dev, void *out_mont_dev, uint64_t out_len, void *hip_stream);
 /* R1CStoQAP::witness_map from the full assignment z (instance variables first, z[0] = 1), all in HBM:
  *   a = A z, b = B z, c = C z on the first num_constraints rows; a[num_constraints + j] = z[j] for j < num_inputs;
