@@ -155,6 +155,9 @@ int pow_tables(DeviceCtx& dc, const Fe<F>& gshift, uint32_t logn, int field, hip
     return ZK_OK;
 }
 
+template <class F>
+int vec_op_run(Fe<F>* a, const Fe<F>* b, const Fe<F>* c, uint64_t n, int op, const Fe<F>& s, hipStream_t st);
+
 // size-2^logn DFT of `a` with root omega; optionally fused with a[i] *= g_pre^i before and a[k] *= g_post^k after
 template <class F>
 int ntt_run(DeviceCtx& dc, int field, Fe<F>* a, uint32_t logn, const Fe<F>& omega, int scale_flag, hipStream_t st, const Fe<F>* g_pre,
@@ -163,7 +166,16 @@ int ntt_run(DeviceCtx& dc, int field, Fe<F>* a, uint32_t logn, const Fe<F>& omeg
     if (!src0) src0 = a;
     if (logn > (uint32_t)F::TWO_ADICITY || logn > 30) return ZK_ERR_INVALID_ARG;   // before anything is sized from logn
     if ((uint32_t)((scale_flag >> 4) & 15) > logn || (scale_flag & ~0xf3)) return ZK_ERR_INVALID_ARG;
-    if (logn == 0) return ZK_OK;  // size-1 transform is the identity, n^-1 = 1 and g^0 = 1
+    if (logn == 0) {   // the size-1 transform is the identity, n^-1 = 1 and g^0 = 1: what is left is where the element lands and its radix
+        if (src0 != a) HIP_TRY(hipMemcpyAsync(a, src0, sizeof(Fe<F>), hipMemcpyDeviceToDevice, st));
+        if (scale_flag & 2) {   // ZK_NTT_OUT_R29: x R -> x R', a factor R' / R = 2^5
+            Fe<F> r;
+            fe_one(r);
+            for (int k = 0; k < F29<F>::W * F29<F>::L - 32 * F::N; k++) fe_dbl(r, r);
+            ZK_TRY(vec_op_run<F>(a, nullptr, nullptr, 1, VEC_SCALE, r, st));
+        }
+        return ZK_OK;
+    }
     // lazy 29-bit limbs inside the tiles (zk_ntt29_kernels.h) unless zk_ntt_opts asks for the saturated words
     const bool lazy = g.ntt_opts.limb_bits != 32;
     PowTables<F> tpre{nullptr, nullptr}, tpost{nullptr, nullptr};

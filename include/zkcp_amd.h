@@ -207,7 +207,11 @@ int zk_msm_batch_device(zk_curve_t c, uint64_t bases_handle, const void *scalars
  * consumer that computes on lazy limbs (zk_expr_eval_lazy_device) -- one constant changes in the last pass, no extra work;
  * ZK_NTT_OUT_SUBCOSETS(lp): result k is stored at (k mod P) * (n / P) + k / P, P = 2^lp -- the P sub-cosets of the output domain
  * one after another (sub-coset j = the points g omega^(i P + j)), which is how a prover that evaluates its quotient sub-coset by
- * sub-coset wants a column (halo2.py EvaluationDomain.coeff_to_extended(parts=)); only the last pass's store addresses change. */
+ * sub-coset wants a column (halo2.py EvaluationDomain.coeff_to_extended(parts=)); only the last pass's store addresses change.
+ * log_n = 0 (one element: the transform, the scaling and both coset shifts are identities) leaves the element as it is on zk_ntt,
+ * zk_ntt_device, zk_ntt_coset_device and zk_ntt_extend_device, copies it from src to dst on the caller's stream on zk_ntt_oop_device,
+ * and on every one of them (zk_ntt hands its argument on as the same bit set) still multiplies it by 2^5 under ZK_NTT_OUT_R29; bad
+ * flags are refused first, as at any size. */
 #define ZK_NTT_OUT_R29 2
 #define ZK_NTT_OUT_SUBCOSETS(log_parts) (((log_parts) & 15) << 4)
 int zk_ntt(zk_field_t f, void *a_mont_host, uint32_t log_n, const void *omega_mont_host, int scale_by_n_inv);
