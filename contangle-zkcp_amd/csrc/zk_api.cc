@@ -1834,6 +1834,66 @@ API int zk_halo2_ipa_compute_b(zk_field_t f, uint32_t k, const void* x, const vo
     });
     return ZK_OK;
 }
+// ---- MockProver::verify on the device (zk_mock.inl) ----
+API int zk_halo2_mock_eval_device(zk_field_t f, uint32_t k, const zk_expr_op* programs, const uint32_t* offsets, uint32_t n_programs,
+                                  const void* const* cols, const uint64_t* poison_from, uint32_t n_cols, const void* consts, uint32_t n_consts,
+                                  void* values_out, uint8_t* status_out, void* stream) {
+    if (!programs || !offsets || !status_out || !aligned16(status_out) || (values_out && !aligned16(values_out)) || (n_cols && (!cols || !poison_from)) ||
+        (n_consts && !consts) || k > 30 || n_programs == 0)
+        return ZK_ERR_INVALID_ARG;
+    if (values_out) {   // 32 bytes per entry in one output, 1 in the other
+        const uintptr_t v0 = (uintptr_t)values_out, s0 = (uintptr_t)status_out, entries = (uintptr_t)n_programs << k;
+        if (v0 < s0 + entries && s0 < v0 + entries * 32) return ZK_ERR_INVALID_ARG;
+    }
+    DEVICE_ENTRY(status_out);
+    FIELD_SWITCH(f, return mock_eval_run<F>(dc, k, programs, offsets, n_programs, cols, poison_from, n_cols, (const Fe<F>*)consts, n_consts,
+                                            (Fe<F>*)values_out, status_out, (hipStream_t)stream));
+    return ZK_ERR_INVALID_ARG;
+}
+API int zk_halo2_mock_lookup_device(zk_field_t f, uint32_t k, const void* inputs_dev, const uint8_t* inputs_status, const void* table_dev,
+                                    const uint8_t* table_status, uint64_t usable_rows, uint8_t* status_out, void* stream) {
+    if (k > 30 || usable_rows > (1ull << k)) return ZK_ERR_INVALID_ARG;
+    FIELD_SWITCH(f, {
+        if (k > (uint32_t)F::TWO_ADICITY) return ZK_ERR_INVALID_ARG;
+    });
+    if (usable_rows) {
+        if (!inputs_dev || !table_dev || !status_out || !aligned16(inputs_dev) || !aligned16(table_dev)) return ZK_ERR_INVALID_ARG;
+        const void* ins[4] = {inputs_dev, table_dev, inputs_status, table_status};
+        const uint64_t bytes[4] = {usable_rows * 32, usable_rows * 32, usable_rows, usable_rows};
+        for (int i = 0; i < 4; i++)
+            if (ins[i]) {
+                const uintptr_t a = (uintptr_t)ins[i], b = (uintptr_t)status_out;
+                if (a < b + usable_rows && b < a + bytes[i]) return ZK_ERR_INVALID_ARG;
+            }
+    }
+    DEVICE_ENTRY(status_out);
+    FIELD_SWITCH(f, return mock_lookup_run<F>(dc, (const Fe<F>*)inputs_dev, inputs_status, (const Fe<F>*)table_dev, table_status, (uint32_t)usable_rows,
+                                              status_out, (hipStream_t)stream));
+    return ZK_ERR_INVALID_ARG;
+}
+API int zk_halo2_mock_permutation_device(zk_field_t f, uint32_t k, uint32_t ncols, const void* const* cols, const uint64_t* poison_from,
+                                         const void* mapping_dev, uint8_t* status_out, void* stream) {
+    if (!cols || !poison_from || !mapping_dev || !status_out || !aligned16(mapping_dev) || ncols == 0 || k > 30) return ZK_ERR_INVALID_ARG;
+    if (((uint64_t)ncols << k) >= (1ull << 32)) return ZK_ERR_INVALID_ARG;       // the assembly's own limit on the number of cells
+    {
+        const uintptr_t m0 = (uintptr_t)mapping_dev, s0 = (uintptr_t)status_out, cells = (uintptr_t)ncols << k;
+        if (m0 < s0 + cells && s0 < m0 + cells * 8) return ZK_ERR_INVALID_ARG;
+    }
+    DEVICE_ENTRY(status_out);
+    FIELD_SWITCH(f, {
+        int bad = 0;
+        ZK_TRY(mock_permutation_run<F>(dc, k, ncols, cols, poison_from, (const uint64_t*)mapping_dev, status_out, &bad, (hipStream_t)stream));
+        return bad ? ZK_ERR_INVALID_ARG : ZK_OK;
+    });
+    return ZK_ERR_INVALID_ARG;
+}
+API int zk_halo2_mock_failures_device(const uint8_t* status_dev, uint64_t n_status, uint64_t cap, uint64_t* positions_out, uint8_t* kinds_out,
+                                      uint64_t* total_out, void* stream) {
+    if (!total_out || (n_status && (!status_dev || !aligned16(status_dev))) || (cap && n_status && (!positions_out || !kinds_out)))
+        return ZK_ERR_INVALID_ARG;
+    DEVICE_ENTRY(status_dev);
+    return mock_failures_run<PallasFp>(dc, status_dev, n_status, cap, positions_out, kinds_out, total_out, (hipStream_t)stream);   // (the bytes carry no field)
+}
 API int zk_expr_eval_device(zk_field_t f, const zk_expr_op* prog, uint32_t n_ops, const void* const* cols, uint32_t n_cols, const void* consts,
                             uint32_t n_consts, uint32_t log_n, uint32_t rot_scale, void* out, void* stream) {
     if (!prog || !out || !aligned16(out) || (n_cols && !cols) || (n_consts && !consts)) return ZK_ERR_INVALID_ARG;

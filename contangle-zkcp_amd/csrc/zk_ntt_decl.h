@@ -102,6 +102,19 @@ int perm_sigmas_run(DeviceCtx& dc, int field, uint32_t k, uint32_t ncols, const 
 // halo2 opening verification (zk_ipa_verify.inl)
 template <class F>
 int ipa_s_run(DeviceCtx& dc, uint32_t k, uint32_t count, const void* u_host, const void* init_host, Fe<F>* s, int accumulate, hipStream_t st);
+// MockProver::verify (zk_mock.inl)
+template <class F>
+int mock_eval_run(DeviceCtx& dc, uint32_t k, const zk_expr_op* prog, const uint32_t* offs, uint32_t n_programs, const void* const* cols,
+                  const uint64_t* poison_from, uint32_t n_cols, const Fe<F>* consts, uint32_t n_consts, Fe<F>* vals, uint8_t* status, hipStream_t st);
+template <class F>
+int mock_failures_run(DeviceCtx& dc, const uint8_t* status, uint64_t N, uint64_t cap, uint64_t* pos_host, uint8_t* kind_host, uint64_t* total_host,
+                      hipStream_t st);
+template <class F>
+int mock_permutation_run(DeviceCtx& dc, uint32_t k, uint32_t ncols, const void* const* cols, const uint64_t* poison_from, const uint64_t* mapping,
+                         uint8_t* status, int* bad_mapping, hipStream_t st);
+template <class F>
+int mock_lookup_run(DeviceCtx& dc, const Fe<F>* A, const uint8_t* a_status, const Fe<F>* S, const uint8_t* s_status, uint32_t u, uint8_t* status,
+                    hipStream_t st);
 template <class F>
 int witness_map_run(DeviceCtx& dc, int field, Fe<F>* a, Fe<F>* b, Fe<F>* c, uint32_t logm, hipStream_t st);
 }  // namespace zk

@@ -44,4 +44,9 @@ template int groth16_key_scalars_run<ZK_FIELD>(DeviceCtx&, const Fe<ZK_FIELD>*, 
 template int perm_sigmas_run<ZK_FIELD>(DeviceCtx&, int, uint32_t, uint32_t, const uint64_t*, const Fe<ZK_FIELD>&, const Fe<ZK_FIELD>&, Fe<ZK_FIELD>*, int*,
                                        hipStream_t);
 template int ipa_s_run<ZK_FIELD>(DeviceCtx&, uint32_t, uint32_t, const void*, const void*, Fe<ZK_FIELD>*, int, hipStream_t);
+template int mock_eval_run<ZK_FIELD>(DeviceCtx&, uint32_t, const zk_expr_op*, const uint32_t*, uint32_t, const void* const*, const uint64_t*, uint32_t,
+                                     const Fe<ZK_FIELD>*, uint32_t, Fe<ZK_FIELD>*, uint8_t*, hipStream_t);
+template int mock_failures_run<ZK_FIELD>(DeviceCtx&, const uint8_t*, uint64_t, uint64_t, uint64_t*, uint8_t*, uint64_t*, hipStream_t);
+template int mock_permutation_run<ZK_FIELD>(DeviceCtx&, uint32_t, uint32_t, const void* const*, const uint64_t*, const uint64_t*, uint8_t*, int*, hipStream_t);
+template int mock_lookup_run<ZK_FIELD>(DeviceCtx&, const Fe<ZK_FIELD>*, const uint8_t*, const Fe<ZK_FIELD>*, const uint8_t*, uint32_t, uint8_t*, hipStream_t);
 }  // namespace zk

@@ -333,13 +333,11 @@ int ipa_update_weights_run(Fe<F>* W, uint64_t m0, uint64_t bit, const Fe<F>& u, 
     return ZK_OK;
 }
 
-// program / column table / constants are copied to the stream's scratch, then one grid-stride launch
-template <class F>
-int expr_eval_run(DeviceCtx& dc, const zk_expr_op* prog, uint32_t n_ops, const void* const* cols, uint32_t n_cols, const Fe<F>* consts,
-                  uint32_t n_consts, uint32_t log_n, uint32_t rot_scale, Fe<F>* out, hipStream_t st) {
-    if (n_ops == 0 || n_ops > EXPR_MAX_OPS || n_cols > EXPR_MAX_COLS || n_consts > EXPR_MAX_CONSTS || log_n > 30) return ZK_ERR_INVALID_ARG;
+// host validation of one stack program, shared by every evaluator that interprets it (expr_eval_run here, mock_eval_run in
+// zk_mock.inl): op codes, stack depth, operand indices, exactly one value left -- a kernel must never index past its tables
+inline int expr_validate(const zk_expr_op* prog, uint32_t n_ops, const void* const* cols, uint32_t n_cols, uint32_t n_consts) {
+    if (n_ops == 0 || n_ops > EXPR_MAX_OPS || n_cols > EXPR_MAX_COLS || n_consts > EXPR_MAX_CONSTS) return ZK_ERR_INVALID_ARG;
     static_assert(sizeof(zk_expr_op) == sizeof(ExprOp), "ABI struct = kernel struct");
-    // validate the program on the host: stack depth, operand indices -- a kernel must never index past its tables
     int depth = 0;
     for (uint32_t k = 0; k < n_ops; k++) {
         const zk_expr_op& o = prog[k];
@@ -351,16 +349,24 @@ int expr_eval_run(DeviceCtx& dc, const zk_expr_op* prog, uint32_t n_ops, const v
         else { if (depth < 2) return ZK_ERR_INVALID_ARG; depth--; }
         if (depth > (int)EXPR_STACK) return ZK_ERR_UNSUPPORTED;
     }
-    if (depth != 1) return ZK_ERR_INVALID_ARG;
+    return depth == 1 ? ZK_OK : ZK_ERR_INVALID_ARG;
+}
+// one aligned 64-bit word per op for the kernels: op | rot << 16 | arg << 32
+inline uint64_t expr_word(const zk_expr_op& o) { return (uint64_t)o.op | ((uint64_t)(uint16_t)o.rot << 16) | ((uint64_t)o.arg << 32); }
+
+// program / column table / constants are copied to the stream's scratch, then one grid-stride launch
+template <class F>
+int expr_eval_run(DeviceCtx& dc, const zk_expr_op* prog, uint32_t n_ops, const void* const* cols, uint32_t n_cols, const Fe<F>* consts,
+                  uint32_t n_consts, uint32_t log_n, uint32_t rot_scale, Fe<F>* out, hipStream_t st) {
+    if (log_n > 30) return ZK_ERR_INVALID_ARG;
+    ZK_TRY(expr_validate(prog, n_ops, cols, n_cols, n_consts));
     StreamScratch* ss = nullptr;
     ZK_TRY(stream_scratch(dc, st, &ss));
     const size_t pb = sizeof(ExprOp) * EXPR_MAX_OPS, cb = sizeof(void*) * EXPR_MAX_COLS, kb = sizeof(Fe<F>) * EXPR_MAX_CONSTS;
     ZK_TRY(ws_get(ss->poly_tot, pb + cb + kb + 64));
     unsigned char* base = (unsigned char*)ss->poly_tot.p;
-    // one aligned 64-bit word per op for the kernel: op | rot << 16 | arg << 32
     std::vector<uint64_t> words(n_ops);
-    for (uint32_t k = 0; k < n_ops; k++)
-        words[k] = (uint64_t)prog[k].op | ((uint64_t)(uint16_t)prog[k].rot << 16) | ((uint64_t)prog[k].arg << 32);
+    for (uint32_t k = 0; k < n_ops; k++) words[k] = expr_word(prog[k]);
     HIP_TRY(hipMemcpyAsync(base, words.data(), sizeof(uint64_t) * n_ops, hipMemcpyHostToDevice, st));
     if (n_cols) HIP_TRY(hipMemcpyAsync(base + pb, cols, sizeof(void*) * n_cols, hipMemcpyHostToDevice, st));
     if (n_consts) HIP_TRY(hipMemcpyAsync(base + pb + cb, consts, sizeof(Fe<F>) * n_consts, hipMemcpyHostToDevice, st));

@@ -23,7 +23,8 @@ PROVER_EXPORTS = ["zk_batch_invert_device", "zk_prefix_product_device", "zk_halo
                   "zk_poly_eval_device", "zk_poly_eval_batch_device", "zk_vec_muladd_device", "zk_vec_muladd_to_device", "zk_kate_division_device", "zk_vec_powers_device", "zk_vec_fold_many_device",
                   "zk_ipa_fold_round_device", "zk_expr_eval_lazy_device", "zk_expr_configure", "zk_expr_specialised_source",
                   "zk_halo2_assembly_new", "zk_halo2_assembly_copy", "zk_halo2_assembly_mapping", "zk_halo2_assembly_free",
-                  "zk_halo2_permutation_sigmas_device", "zk_halo2_ipa_s_device", "zk_halo2_ipa_compute_b"]
+                  "zk_halo2_permutation_sigmas_device", "zk_halo2_ipa_s_device", "zk_halo2_ipa_compute_b",
+                  "zk_halo2_mock_eval_device", "zk_halo2_mock_lookup_device", "zk_halo2_mock_permutation_device", "zk_halo2_mock_failures_device"]
 
 
 def best_multiexp(coeffs, bases):
@@ -360,6 +361,10 @@ def _plib():
     lib.zk_halo2_permutation_sigmas_device.argtypes = [i32, u32, u32, vp, vp, vp, vp]
     lib.zk_halo2_ipa_s_device.argtypes = [i32, u32, u32, vp, vp, vp, i32, vp]
     lib.zk_halo2_ipa_compute_b.argtypes = [i32, u32, vp, vp, vp]
+    lib.zk_halo2_mock_eval_device.argtypes = [i32, u32, ctypes.POINTER(ExprOp), vp, u32, pp, vp, u32, vp, u32, vp, vp, vp]
+    lib.zk_halo2_mock_lookup_device.argtypes = [i32, u32, vp, vp, vp, vp, u64, vp, vp]
+    lib.zk_halo2_mock_permutation_device.argtypes = [i32, u32, u32, pp, vp, vp, vp, vp]
+    lib.zk_halo2_mock_failures_device.argtypes = [vp, u64, u64, vp, vp, vp, vp]
     return lib
 
 
@@ -1250,3 +1255,312 @@ def verify_batch(params, items, weights, stream=0):
     """true when every opening of the batch verifies (up to the soundness of the random weights): batch_msm(..).eval() -- one
     pass for all the g_scalars, one n-point MSM"""
     return batch_msm(params, items, weights, stream=stream).eval()
+
+
+# ------------------------------------------------------------------ MockProver (dev.rs), after synthesis
+MOCK_MAX_PROGRAMS = 1024       # csrc/zk_mock_kernels.h: programs per zk_halo2_mock_eval_device call (more are chunked here)
+MOCK_ZERO, MOCK_NONZERO, MOCK_POISON = 0, 1, 2
+
+
+class _Failure:
+    """one VerifyFailure of dev.rs: equal when class and fields are"""
+    _fields = ()
+
+    def _key(self):
+        return tuple(getattr(self, f) for f in self._fields)
+
+    def __eq__(self, other):
+        return type(other) is type(self) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash((type(self).__name__,) + tuple(map(str, self._key())))
+
+    def __repr__(self):
+        return "%s(%s)" % (type(self).__name__, ", ".join("%s=%r" % (f, getattr(self, f)) for f in self._fields))
+
+
+class ConstraintNotSatisfied(_Failure):
+    """gate: (index, name); poly: index inside the gate; row; cell_values: [((column, rotation), integer), ...] -- the cells the
+    polynomial queries at that row, in order of first appearance, as canonical integers"""
+    _fields = ("gate", "poly", "row", "cell_values")
+
+    def __init__(self, gate, poly, row, cell_values):
+        self.gate, self.poly, self.row, self.cell_values = tuple(gate), int(poly), int(row), list(cell_values)
+
+
+class ConstraintPoisoned(_Failure):
+    """an active constraint reads a poisoned cell (a blinding row of an advice column); once per constraint"""
+    _fields = ("gate", "poly")
+
+    def __init__(self, gate, poly):
+        self.gate, self.poly = tuple(gate), int(poly)
+
+
+class Lookup(_Failure):
+    _fields = ("lookup", "row")
+
+    def __init__(self, lookup, row):
+        self.lookup, self.row = int(lookup), int(row)
+
+
+class Permutation(_Failure):
+    """column: the flat column index (advice ++ fixed ++ instance)"""
+    _fields = ("column", "row")
+
+    def __init__(self, column, row):
+        self.column, self.row = int(column), int(row)
+
+
+class VerifyFailures(AssertionError):
+    """MockProver.assert_satisfied: carries the list"""
+
+    def __init__(self, failures, truncated):
+        AssertionError.__init__(self, "circuit was not satisfied%s:\n  %s" % (" (list truncated)" if truncated else "", "\n  ".join(map(repr, failures[:32]))))
+        self.failures, self.truncated = failures, truncated
+
+
+def _bytes_buffer(count):
+    """zero device buffer of status bytes"""
+    from .groth16 import _on_emulator
+    if _on_emulator():
+        return np.zeros(max(count, 1), dtype=np.uint8)
+    import torch
+    return torch.zeros(max(count, 1), dtype=torch.uint8, device="cuda")
+
+
+def mock_eval(field, k, programs, columns, poison_from, consts, status=None, values=None, want_values=False, stream=0):
+    """zk_halo2_mock_eval_device: `programs` (tuple form, see evaluate_expression) at every row of the 2^k-row domain, three-valued.
+    columns: device buffers [2^k, 4]; poison_from: one row per column.  Returns (status [P * 2^k] bytes, values [P, 2^k, 4] or None),
+    device buffers."""
+    from .groth16 import _new_buffer
+    n, P = 1 << k, len(programs)
+    ops = _expr_ops([o for prog in programs for o in prog])
+    offs = np.zeros(P + 1, dtype=np.uint32)
+    offs[1:] = np.cumsum([len(prog) for prog in programs])
+    status = _bytes_buffer(P * n) if status is None else status
+    if want_values and values is None:
+        values = _new_buffer((max(P, 1), n, 4))
+    cs = _np64(consts).reshape(-1, 4) if len(consts) else np.zeros((1, 4), dtype=np.uint64)
+    pf = np.ascontiguousarray(poison_from, dtype=np.uint64)
+    cols = _ptr_array(columns)
+    for lo in range(0, max(P, 1), MOCK_MAX_PROGRAMS):          # (P = 0 goes down once and is refused there)
+        hi = min(P, lo + MOCK_MAX_PROGRAMS)
+        o = np.ascontiguousarray(offs[lo:hi + 1] - offs[lo]) if P else offs
+        sub = ctypes.cast(ctypes.addressof(ops) + int(offs[lo]) * ctypes.sizeof(ExprOp), ctypes.POINTER(ExprOp))
+        vout = None if values is None else ctypes.c_void_p(_ptr(values).value + lo * n * 32)
+        _check(_plib().zk_halo2_mock_eval_device(field_id(field), int(k), sub, _ptr(o), hi - lo, cols, _ptr(pf), len(columns), _ptr(cs), len(consts),
+                                                 vout, ctypes.c_void_p(_ptr(status).value + lo * n), ctypes.c_void_p(stream)),
+               "zk_halo2_mock_eval_device")
+    return status, values
+
+
+def mock_failures(status, count, cap, stream=0):
+    """zk_halo2_mock_failures_device: (positions uint64 [m], kinds uint8 [m], total) of the non-zero bytes of status[0 .. count),
+    m = min(total, cap), ascending"""
+    cap = int(min(cap, count))
+    pos, kinds, total = np.zeros(max(cap, 1), dtype=np.uint64), np.zeros(max(cap, 1), dtype=np.uint8), ctypes.c_uint64(0)
+    _check(_plib().zk_halo2_mock_failures_device(_ptr(status), int(count), cap, _ptr(pos), _ptr(kinds), ctypes.byref(total), ctypes.c_void_p(stream)),
+           "zk_halo2_mock_failures_device")
+    m = min(total.value, cap)
+    return pos[:m], kinds[:m], total.value
+
+
+def _program_cells(program):
+    """the (column, rotation) queries of a program, in order of first appearance"""
+    seen = []
+    for o in program:
+        if o[0] == "col" and (int(o[1]), int(o[2])) not in seen:
+            seen.append((int(o[1]), int(o[2])))
+    return seen
+
+
+class MockProver:
+    """halo2_proofs 0.2 dev.rs MockProver, after synthesis: does this assignment satisfy these gates, lookups and copy constraints?
+    The semantics (Poison cells in the advice columns' blinding rows, three-valued evaluation, the order of the list, where this
+    knowingly differs from upstream) are DESIGN.md §5 "MockProver".
+
+      advice, fixed   device columns [n, 4] Montgomery (a list of them, or one [count, n, 4] buffer)
+      instance        per column at most `usable` values -- Python integers, or Montgomery limbs [m, 4] -- zero-padded on upload;
+                      more than that is upstream's InstanceTooLarge (ValueError)
+      gates           [(name, [program, ...]), ...]; programs in the tuple form of evaluate_expression over the flat column space
+                      advice ++ fixed ++ instance
+      lookups         [(input_programs, table_programs), ...], equally long lists.  One expression wide: the membership test runs
+                      on the device (zk_halo2_mock_lookup_device).  Wider: the expressions are evaluated on the device, the
+                      tuples are compared ON THE HOST with Python integers (the device path for tuples is DESIGN.md's follow-up).
+      permutation     (flat column indices, Assembly or [ncols, n] uint64 mapping array)
+      consts          Montgomery limbs [count, 4], shared by all programs"""
+
+    def __init__(self, field, k, blinding_factors, advice, fixed, instance=(), gates=(), lookups=(), permutation=None, consts=(), stream=0):
+        from .groth16 import _upload
+        self.field, self.k, self.n, self.blinding_factors, self.stream = field_id(field), int(k), 1 << int(k), int(blinding_factors), stream
+        if self.n < self.blinding_factors + 3:       # upstream: cs.minimum_rows() -> Error::NotEnoughRowsAvailable
+            raise ValueError("NotEnoughRowsAvailable: n = %d < blinding_factors + 3 = %d" % (self.n, self.blinding_factors + 3))
+        self.usable = self.n - (self.blinding_factors + 1)
+        p = field_modulus(field)
+
+        def columns_of(group):
+            cols = [group[i] for i in range(len(group))]
+            for c in cols:
+                if tuple(c.shape) != (self.n, 4):
+                    raise AssertionError("assertion failed: column.len() == 1 << k")
+            return cols
+
+        inst = np.zeros((len(instance), self.n, 4), dtype=np.uint64)
+        for i, col in enumerate(instance):
+            if len(col) > self.usable:
+                raise ValueError("InstanceTooLarge: instance column %d has %d values, %d rows are usable" % (i, len(col), self.usable))
+            if isinstance(col, np.ndarray) and col.ndim == 2:
+                inst[i, :len(col)] = _np64(col)
+            else:
+                for r, v in enumerate(col):
+                    inst[i, r] = _mont_limbs(int(v) % p, p)
+        self._instance = _upload(inst) if len(instance) else None
+        self.columns = columns_of(advice) + columns_of(fixed) + ([self._instance[i] for i in range(len(instance))] if len(instance) else [])
+        self.n_advice, self.n_fixed, self.n_instance = len(advice), len(fixed), len(instance)
+        self.poison_from = np.array([self.usable] * self.n_advice + [self.n] * (self.n_fixed + self.n_instance), dtype=np.uint64)
+        self.consts = _np64(consts).reshape(-1, 4) if len(consts) else np.zeros((0, 4), dtype=np.uint64)
+        self.gates = [(name, [list(prog) for prog in polys]) for name, polys in gates]
+        self.lookups = [([list(q) for q in ins], [list(q) for q in tab]) for ins, tab in lookups]
+        for _, polys in self.gates:
+            for prog in polys:
+                self._check_program(prog)
+        for ins, tab in self.lookups:
+            if len(ins) != len(tab) or not ins:
+                raise ZkError(ZK_ERR_INVALID_ARG, "a lookup is a pair of equally long, non-empty lists of programs")
+            for prog in ins + tab:
+                self._check_program(prog)
+        self.permutation = None
+        if permutation is not None:
+            idx, asm = permutation
+            mapping = asm.mapping() if isinstance(asm, Assembly) else asm
+            if any(not 0 <= int(c) < len(self.columns) for c in idx) or tuple(mapping.shape) != (len(idx), self.n):
+                raise ZkError(ZK_ERR_INVALID_ARG, "permutation: column indices / mapping shape")
+            self.permutation = ([int(c) for c in idx], _upload(mapping) if isinstance(mapping, np.ndarray) else mapping)
+        self.failure_counts, self.truncated = {}, False
+
+    def _check_program(self, prog):
+        _expr_ops(prog)                              # the range checks of every field of every op
+        for o in prog:
+            if o[0] == "col" and int(o[1]) >= len(self.columns):
+                raise ZkError(ZK_ERR_INVALID_ARG, "expression op %r: no such column" % (o,))
+            if o[0] in ("const", "scale") and int(o[1]) >= len(self.consts):
+                raise ZkError(ZK_ERR_INVALID_ARG, "expression op %r: no such constant" % (o,))
+
+    def _eval(self, programs, want_values=False):
+        return mock_eval(self.field, self.k, programs, self.columns, self.poison_from, self.consts, want_values=want_values, stream=self.stream)
+
+    def _cell_values(self, wanted):
+        """wanted: [(column, row), ...] -> integers; one gather per column group"""
+        from .groth16 import _download
+        if not wanted:
+            return []
+        p = field_modulus(self.field)
+        r_inv = pow(1 << 256, -1, p)
+        out = [None] * len(wanted)
+        by_col = {}
+        for i, (c, r) in enumerate(wanted):
+            by_col.setdefault(c, []).append((i, r))
+        for c, items in by_col.items():
+            rows = np.array([r for _, r in items], dtype=np.int64)
+            col = self.columns[c]
+            if isinstance(col, np.ndarray):
+                got = col[rows]
+            else:
+                import torch
+                got = _download(col[torch.from_numpy(rows).to(col.device)])
+            for (i, _), limbs in zip(items, _np64(got).tolist()):
+                out[i] = sum(w << (64 * j) for j, w in enumerate(limbs)) * r_inv % p
+        return out
+
+    def _verify_gates(self, cap):
+        index = [(g, j) for g, (_, polys) in enumerate(self.gates) for j in range(len(polys))]
+        if not index:
+            return [], 0
+        status, _ = self._eval([self.gates[g][1][j] for g, j in index])
+        pos, kinds, total = mock_failures(status, len(index) * self.n, cap, self.stream)
+        found, poisoned, wanted = [], set(), []
+        for q, kind in zip(pos.tolist(), kinds.tolist()):
+            g, j = index[q // self.n]
+            row = q % self.n
+            if kind == MOCK_POISON:
+                if (g, j) not in poisoned:               # once per constraint, at the position of its first poisoned row
+                    poisoned.add((g, j))
+                    found.append((g, row, j, None))
+            else:
+                cells = _program_cells(self.gates[g][1][j])
+                found.append((g, row, j, (len(wanted), cells)))
+                wanted.extend((c, (row + rot) % self.n) for c, rot in cells)
+        values = self._cell_values(wanted)
+        out = []
+        for g, row, j, cells in sorted(found, key=lambda f: f[:3]):
+            gate = (g, self.gates[g][0])
+            if cells is None:
+                out.append(ConstraintPoisoned(gate, j))
+            else:
+                out.append(ConstraintNotSatisfied(gate, j, row, list(zip(cells[1], values[cells[0]:cells[0] + len(cells[1])]))))
+        return out, total
+
+    def _verify_lookups(self, cap):
+        from .groth16 import _download
+        if not self.lookups:
+            return [], 0
+        n, u = self.n, self.usable
+        programs, first = [], []
+        for ins, tab in self.lookups:
+            first.append(len(programs))
+            programs.extend(ins + tab)
+        status, values = self._eval(programs, want_values=True)
+        out_status = _bytes_buffer(len(self.lookups) * n)
+        host = {}
+        sbase, obase = _ptr(status).value, _ptr(out_status).value
+        for li, (ins, tab) in enumerate(self.lookups):
+            a = first[li]
+            if len(ins) == 1:
+                _check(_plib().zk_halo2_mock_lookup_device(self.field, self.k, _ptr(values[a]), ctypes.c_void_p(sbase + a * n), _ptr(values[a + 1]),
+                                                           ctypes.c_void_p(sbase + (a + 1) * n), u, ctypes.c_void_p(obase + li * n),
+                                                           ctypes.c_void_p(self.stream)), "zk_halo2_mock_lookup_device")
+            else:                                        # HOST PATH: tuples of Python integers; Poison is its own component value
+                w = len(ins)
+                vals = _np64(_download(values[a:a + 2 * w]))[:, :u].astype(object)
+                ints = vals[..., 0] + (vals[..., 1] << 64) + (vals[..., 2] << 128) + (vals[..., 3] << 192)
+                st = status[a * n:(a + 2 * w) * n]
+                st = (st if isinstance(st, np.ndarray) else st.cpu().numpy()).reshape(2 * w, n)[:, :u]      # (after _download's synchronisation)
+                comp = lambda e, r: None if st[e, r] == MOCK_POISON else ints[e, r]
+                table = {tuple(comp(w + e, r) for e in range(w)) for r in range(u)}
+                host[li] = [r for r in range(u) if tuple(comp(e, r) for e in range(w)) not in table]
+        pos, _, total = mock_failures(out_status, len(self.lookups) * n, cap, self.stream)
+        found = [(int(q) // n, int(q) % n) for q in pos.tolist()]
+        for li, rows in host.items():
+            found.extend((li, r) for r in rows)
+            total += len(rows)
+        found.sort()
+        return [Lookup(li, r) for li, r in found[:cap]], total
+
+    def _verify_permutation(self, cap):
+        if self.permutation is None:
+            return [], 0
+        idx, mapping = self.permutation
+        status = _bytes_buffer(len(idx) * self.n)
+        pf = np.ascontiguousarray(self.poison_from[idx], dtype=np.uint64)
+        _check(_plib().zk_halo2_mock_permutation_device(self.field, self.k, len(idx), _ptr_array([self.columns[c] for c in idx]), _ptr(pf), _ptr(mapping),
+                                                        _ptr(status), ctypes.c_void_p(self.stream)), "zk_halo2_mock_permutation_device")
+        pos, _, total = mock_failures(status, len(idx) * self.n, cap, self.stream)
+        return [Permutation(idx[int(q) // self.n], int(q) % self.n) for q in pos.tolist()], total
+
+    def verify(self, max_failures=65536):
+        """dev.rs MockProver::verify: gate failures in (gate, row, poly) order, then lookup failures in (lookup, row) order, then
+        permutation failures in (column, row) order; [] is upstream's Ok(()).  failure_counts: the totals per class as the device
+        counted them -- "gates" = flagged (constraint, row) pairs, every poisoned row of a constraint included; when a class has
+        more than max_failures the first ones in device order (program, then row) are reported and `truncated` is set."""
+        cap = int(max_failures)
+        gates, n_g = self._verify_gates(cap)
+        lookups, n_l = self._verify_lookups(cap)
+        perm, n_p = self._verify_permutation(cap)
+        self.failure_counts = {"gates": n_g, "lookups": n_l, "permutation": n_p}
+        self.truncated = any(t > cap for t in (n_g, n_l, n_p))
+        return gates + lookups + perm
+
+    def assert_satisfied(self, max_failures=65536):
+        failures = self.verify(max_failures)
+        if failures:
+            raise VerifyFailures(failures, self.truncated)

@@ -370,6 +370,57 @@ int zk_expr_eval_lazy_device(zk_field_t f, const zk_expr_op *program_host, uint3
                              const void *consts_mont_host, uint32_t n_consts, uint32_t log_n_ext, uint32_t rot_scale, void *out_dev,
                              void *hip_stream);
 
+/* ---- MockProver::verify on the device (halo2_proofs 0.2 dev.rs; the reference's only halo2 call is MockProver::run(12, ..) at
+ * circuits-halo2/src/encryption.rs:335) ----
+ * Does an assignment satisfy a circuit?  Four entries: the three-valued evaluation of gate / lookup expressions, the lookup
+ * membership test, the copy-constraint check, and the compaction of a status array into a failure list.  The semantics -- Poison
+ * cells, where they deliberately differ from upstream -- are DESIGN.md §5 "MockProver"; contangle-zkcp_amd/halo2.py MockProver puts them together.
+ * Every entry refuses with ZK_ERR_INVALID_ARG before it launches anything (null or misaligned pointers, overlapping outputs, k above
+ * the field's two-adicity or above 30, an invalid program, poison_from > 2^k, usable_rows > 2^k) and leaves the library usable.
+ *
+ * zk_halo2_mock_eval_device: n_programs stack programs (the zk_expr_op set above, rotations in rows, cyclic mod 2^k) at every row of
+ * the 2^k-row domain, in one launch.  A value is Real(v) or Poison: the cell of column c at a row >= poison_from[c] is Poison; neg
+ * keeps the kind; add / sub with a Poison side are Poison; Real(0) * Poison = Real(0) in either order, Real(non-zero) * Poison and
+ * Poison * Poison are Poison; scale by the constant 0 makes Poison Real(0), any other constant leaves it Poison.
+ *   programs_host   the programs back to back; offsets_host[p] .. offsets_host[p + 1] are program p's ops (n_programs + 1 entries,
+ *                   offsets_host[0] = 0, increasing).  Each program: the validation and limits of zk_expr_eval_device (<= 512 ops,
+ *                   stack <= 8, <= 64 columns, <= 32 constants, exactly one value left); at most 1024 programs a call.
+ *   columns_dev     host array of n_columns device pointers, each 2^k Montgomery elements, 16-B aligned; poison_from_host: n_columns
+ *                   rows, each <= 2^k (2^k = never); consts_mont_host: n_consts elements, canonical Montgomery
+ *   status_out_dev  n_programs x 2^k bytes, 16-B aligned: status[p * 2^k + i] = 0 Real zero, 1 Real non-zero, 2 Poison
+ *   values_out_dev  optional (NULL), n_programs x 2^k elements, 16-B aligned: the value, 0 at a Poison entry
+ * Stored cells are taken mod p (a word in [p, 2p) counts as its residue), so the zero test is exact.  Reads the host arrays before it
+ * returns (one synchronisation of hip_stream, before the launch); the kernel itself is only enqueued.  Scratch: 8 B per op. */
+int zk_halo2_mock_eval_device(zk_field_t f, uint32_t k, const zk_expr_op *programs_host, const uint32_t *offsets_host, uint32_t n_programs,
+                              const void *const *columns_dev, const uint64_t *poison_from_host, uint32_t n_columns, const void *consts_mont_host,
+                              uint32_t n_consts, void *values_out_dev, uint8_t *status_out_dev, void *hip_stream);
+/* A lookup one expression wide, exact: status_out_dev[r] = 1 iff the input of row r < usable_rows is not among the table values of
+ * rows [0, usable_rows), else 0; usable_rows bytes are written, rows from usable_rows on are neither read nor written.
+ * inputs_dev / table_dev: Montgomery elements, 16-B aligned (the values_out of the evaluator); inputs_status_dev / table_status_dev
+ * (optional, NULL = all Real): the evaluator's status bytes, where 2 marks a Poison entry.  Poison compares as upstream's derived
+ * order has it, equal to Poison and above every field element: a Poison input passes iff the table holds a Poison entry.
+ * The table's canonical values are sorted by the LSD passes of zk_halo2_permute_expression_pair_device, then one lane per input row
+ * searches them.  Does not synchronise.  Scratch: 64 B per usable row, owned by the stream.  usable_rows = 0 does nothing. */
+int zk_halo2_mock_lookup_device(zk_field_t f, uint32_t k, const void *inputs_dev, const uint8_t *inputs_status_dev, const void *table_dev,
+                                const uint8_t *table_status_dev, uint64_t usable_rows, uint8_t *status_out_dev, void *hip_stream);
+/* The copy constraints: over the permutation's ncols columns (columns_dev: host array of device pointers, 2^k Montgomery elements
+ * each; poison_from_host as above) and the Assembly mapping (mapping_dev: ncols x 2^k words, column << 32 | row, device, 16-B aligned
+ * -- what zk_halo2_assembly_mapping hands out),
+ *   status_out_dev[c * 2^k + r] = 1 iff mapping[c][r] != (c, r) and (either end is Poison or the two stored values differ), else 0.
+ * Stored values are compared as stored.  The mapping is device data the library did not produce: a word that names a row >= 2^k or a
+ * column >= ncols is never used as an index, its cell gets 0, and the call returns ZK_ERR_INVALID_ARG; the library stays usable (the
+ * contract of zk_halo2_permutation_sigmas_device).  ncols = 0 or 2^k * ncols >= 2^32 is refused.  Synchronises hip_stream twice: after
+ * copying the tables, and at the end to read the status word. */
+int zk_halo2_mock_permutation_device(zk_field_t f, uint32_t k, uint32_t ncols, const void *const *columns_dev, const uint64_t *poison_from_host,
+                                     const void *mapping_dev, uint8_t *status_out_dev, void *hip_stream);
+/* The failure list of a status array: positions_out_host[q] / kinds_out_host[q] = the index and the byte of the q-th non-zero byte of
+ * status_dev[0 .. n_status) for q < min(*total_out_host, cap), ascending; *total_out_host = the number of non-zero bytes.  Entries past
+ * min(total, cap) of the two host arrays are not touched.  status_dev: 16-B aligned (it is read 16 bytes at a time).  The same list
+ * on every run: positions come from a reduce / scan / emit sequence, not from atomics.  Synchronises hip_stream once, at the end.
+ * Scratch: 12 B per 4096 status bytes and 9 B per reported entry. */
+int zk_halo2_mock_failures_device(const uint8_t *status_dev, uint64_t n_status, uint64_t cap, uint64_t *positions_out_host, uint8_t *kinds_out_host,
+                                  uint64_t *total_out_host, void *hip_stream);
+
 /* A gate expression is fixed per proving key: for evaluations of 2^16 rows and more zk_expr_eval_lazy_device writes the annotated
  * program out as straight-line HIP (the stack resolved at generation time: no interpreter, no LDS), compiles it once per
  * (program, device) with hiprtc -- ~10 s for the reference circuit's 268 operations; the headers it includes ship next to the

@@ -275,6 +275,15 @@ extern "C" {
     pub fn zk_halo2_assembly_free(handle: u64) -> c_int;
     pub fn zk_halo2_permutation_sigmas_device(f: c_int, k: u32, ncols: u32, mapping_dev: *const c_void, delta_mont_host: *const c_void,
                                               sigmas_dev: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn zk_halo2_mock_eval_device(f: c_int, k: u32, programs_host: *const zk_expr_op, offsets_host: *const u32, n_programs: u32,
+                                     columns_dev: *const *const c_void, poison_from_host: *const u64, n_columns: u32, consts_mont_host: *const c_void,
+                                     n_consts: u32, values_out_dev: *mut c_void, status_out_dev: *mut u8, hip_stream: *mut c_void) -> c_int;
+    pub fn zk_halo2_mock_lookup_device(f: c_int, k: u32, inputs_dev: *const c_void, inputs_status_dev: *const u8, table_dev: *const c_void,
+                                       table_status_dev: *const u8, usable_rows: u64, status_out_dev: *mut u8, hip_stream: *mut c_void) -> c_int;
+    pub fn zk_halo2_mock_permutation_device(f: c_int, k: u32, ncols: u32, columns_dev: *const *const c_void, poison_from_host: *const u64,
+                                            mapping_dev: *const c_void, status_out_dev: *mut u8, hip_stream: *mut c_void) -> c_int;
+    pub fn zk_halo2_mock_failures_device(status_dev: *const u8, n_status: u64, cap: u64, positions_out_host: *mut u64, kinds_out_host: *mut u8,
+                                         total_out_host: *mut u64, hip_stream: *mut c_void) -> c_int;
     pub fn zk_inner_product_device(f: c_int, a_dev: *const c_void, b_dev: *const c_void, n: u64, out_mont_host: *mut c_void,
                                    hip_stream: *mut c_void) -> c_int;
     pub fn zk_poly_eval_device(f: c_int, coeffs_dev: *const c_void, n: u64, x_mont_host: *const c_void, out_mont_host: *mut c_void,
