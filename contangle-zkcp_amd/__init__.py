@@ -279,6 +279,18 @@ class Bases:
         """build the table of window multiples for msm(..., precomputed=True)"""
         _check(load().zk_bases_precompute(self.handle, window_bits), "zk_bases_precompute")
 
+    def precompute_shifts(self):
+        """build the shift tables [2^64] P, [2^128] P, [2^192] P of the generator collapse (halo2.IpaProverVirtual.collapse): once,
+        where the key is loaded -- otherwise the second collapse over a large handle builds them"""
+        from . import halo2
+        _check(halo2._plib().zk_bases_precompute_shifts(self.curve, self.handle), "zk_bases_precompute_shifts")
+
+    def has_shift_tables(self):
+        from . import halo2
+        out = ctypes.c_uint64(0)
+        _check(halo2._plib().zk_bases_shift_tables(self.handle, ctypes.byref(out)), "zk_bases_shift_tables")
+        return bool(out.value)
+
     def refresh(self, offset, count, stream=0):
         """points [offset, offset + count) of the adopted device buffer were rewritten on `stream`: update the derived copies"""
         _check(load().zk_bases_refresh(self.handle, offset, count, ctypes.c_void_p(stream)), "zk_bases_refresh")

@@ -58,6 +58,14 @@ int stream_scratch(DeviceCtx& dc, hipStream_t st, StreamScratch** out) {
     *out = victim;
     return ZK_OK;
 }
+// ZK_IPA_SHIFT_TABLES=0: the generator collapse never builds or reads shift tables (A/B against the table-free path)
+bool ipa_shift_tables_enabled() {
+    static const bool on = [] {
+        const char* e = getenv("ZK_IPA_SHIFT_TABLES");
+        return !(e && e[0] == '0' && e[1] == 0);
+    }();
+    return on;
+}
 }  // namespace zk
 
 namespace {
@@ -527,6 +535,7 @@ API int zk_shutdown(void) {
             if (kv.second.per_dev[d].owned) hipFree(kv.second.per_dev[d].dev);
             if (kv.second.per_dev[d].dev29) hipFree(kv.second.per_dev[d].dev29);
             if (kv.second.per_dev[d].pre) hipFree(kv.second.per_dev[d].pre);
+            if (kv.second.per_dev[d].shift) hipFree(kv.second.per_dev[d].shift);
         }
     g.bases.clear();
     g.tickets.clear();
@@ -661,6 +670,7 @@ API int zk_bases_free(uint64_t handle) {
         if (bc.owned) hipFree(bc.dev);
         if (bc.dev29) hipFree(bc.dev29);
         if (bc.pre) hipFree(bc.pre);
+        if (bc.shift) hipFree(bc.shift);
     }
     hipSetDevice(g.devs[0]->device);
     g.bases.erase(it);
@@ -681,6 +691,43 @@ API int zk_bases_precompute(uint64_t handle, int window_bits) {
         CURVE_SWITCH(c, st = bases_precompute_run<C>(be.per_dev[d], be.n, cw));
         ZK_TRY(st);
     }
+    return ZK_OK;
+}
+// under g.mu.  Drops the copy's shift tables (the points changed, or the handle goes away)
+static void shifts_drop(BasesCopy& bc) {
+    if (bc.shift) {
+        hipDeviceSynchronize();
+        hipFree(bc.shift);
+    }
+    bc.shift = nullptr;
+    bc.collapses = 0;
+    bc.shift_failed = false;
+}
+API int zk_bases_precompute_shifts(zk_curve_t c, uint64_t handle) {
+    std::lock_guard<std::mutex> lk(g.mu);
+    ZK_TRY(require_init());
+    auto it = g.bases.find(handle);
+    if (it == g.bases.end()) return ZK_ERR_BAD_HANDLE;
+    BasesEntry& be = it->second;
+    if (be.curve != (int)c) return ZK_ERR_INVALID_ARG;
+    if (!ipa_shift_tables_enabled()) return ZK_OK;
+    int st = ZK_OK;
+    for (size_t d = 0; d < be.per_dev.size() && st == ZK_OK; d++) {
+        st = bind_device(*g.devs[d]);
+        if (st == ZK_OK && !be.per_dev[d].shift) CURVE_SWITCH(c, st = bases_shifts_run<C>(be.per_dev[d], be.n));
+    }
+    hipSetDevice(g.devs[0]->device);
+    return st;
+}
+API int zk_bases_shift_tables(uint64_t handle, uint64_t* present) {
+    std::lock_guard<std::mutex> lk(g.mu);
+    ZK_TRY(require_init());
+    if (!present) return ZK_ERR_INVALID_ARG;
+    auto it = g.bases.find(handle);
+    if (it == g.bases.end()) return ZK_ERR_BAD_HANDLE;
+    uint64_t all = 1;
+    for (const BasesCopy& bc : it->second.per_dev) all &= bc.shift ? 1 : 0;
+    *present = all;
     return ZK_OK;
 }
 API int zk_bases_refresh(uint64_t handle, uint64_t offset, uint64_t count, void* stream) {
@@ -713,6 +760,7 @@ API int zk_bases_refresh(uint64_t handle, uint64_t offset, uint64_t count, void*
 #endif
             st = nullptr;
         }
+        shifts_drop(be.per_dev[d]);
         CURVE_SWITCH(c, ZK_TRY(bases_refresh_run<C>(be.per_dev[d], offset, count, st)));
         if ((int)d != src) HIP_TRY(hipStreamSynchronize(nullptr));
     }
@@ -1750,8 +1798,20 @@ API int zk_ipa_collapse_range_device(zk_curve_t c, uint64_t handle, const void* 
         if (it == g.bases.end()) return ZK_ERR_BAD_HANDLE;
         if (it->second.curve != (int)c) return ZK_ERR_INVALID_ARG;
         dcp = &device_of(g_out);
-        bc = &it->second.per_dev[dcp->index];
+        BasesCopy& mine = it->second.per_dev[dcp->index];
         base_n = it->second.n;
+        // the second collapse over a large handle that was not rewritten in between builds its shift tables: a resident key pays once
+        // (the first call runs the table-free path, so a handle that is collapsed once and dropped never pays); no memory, no tables
+        if (mine.collapses++ >= 1 && !mine.shift && !mine.shift_failed && base_n >= ZK_SHIFT_AUTO_MIN && ipa_shift_tables_enabled() &&
+            bind_device(*dcp) == ZK_OK) {
+            int st = ZK_ERR_UNSUPPORTED;
+            CURVE_SWITCH(c, st = bases_shifts_run<C>(mine, base_n));
+            if (st != ZK_OK) {
+                mine.shift_failed = true;
+                (void)hipGetLastError();
+            }
+        }
+        bc = &mine;
     }
     DeviceCtx& dc = *dcp;
     ZK_TRY(bind_device(dc));

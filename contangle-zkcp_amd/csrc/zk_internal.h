@@ -51,7 +51,14 @@ struct BasesCopy {
     bool owned = false;
     void* pre = nullptr;     // optional (zk_bases_precompute): [2^(c w)] P_i for every window w, lazy-limb view, window-major
     int pre_c = 0, pre_w = 0;
+    void* shift = nullptr;   // optional (zk_bases_precompute_shifts, or built by the second collapse over a large handle): [2^(64 k)] P_i, k < 4,
+                             // lazy-limb view, [4][n] (k = 0 repeats dev29): the generator collapse reads 64-bit scalar chunks over it
+    int collapses = 0;       // zk_ipa_collapse_* calls over this copy since it was installed or last refreshed
+    bool shift_failed = false;   // the automatic build ran out of memory once: not tried again
 };
+constexpr int ZK_SHIFT_TABLES = 4;                 // 64-bit chunks of a scalar
+constexpr uint64_t ZK_SHIFT_AUTO_MIN = 1ull << 16; // smallest handle the collapse builds shift tables for by itself
+bool ipa_shift_tables_enabled();                   // ZK_IPA_SHIFT_TABLES=0 in the environment turns the table path off (zk_api.cc)
 struct BasesEntry {
     int curve;
     uint64_t n;

@@ -552,6 +552,27 @@ int bases_precompute_run(BasesCopy& bc, uint64_t n, int c) {
     return ZK_ERR_UNSUPPORTED;
 }
 
+// the shift tables of the generator collapse (zk_bases_precompute_shifts): the same kernel with 64-bit "windows", [4][n] points
+template <class C>
+int bases_shifts_run(BasesCopy& bc, uint64_t n) {
+    if constexpr (has_f29<C>()) {
+        if (n == 0 || n * (uint64_t)ZK_SHIFT_TABLES >= (1ull << 31)) return ZK_ERR_UNSUPPORTED;
+        if (bc.shift) hipFree(bc.shift);
+        bc.shift = nullptr;
+        void* d = nullptr;
+        HIP_TRY(hipMalloc(&d, sizeof(StoredAffine<F29View<C>>) * n * ZK_SHIFT_TABLES));
+        ZK_LAUNCH((bases_precompute_kernel<C>), (unsigned)((n + 63) / 64), 64, 0, (hipStream_t)0, (const Affine<C>*)bc.dev,
+                  (StoredAffine<F29View<C>>*)d, (uint32_t)n, 64u, (uint32_t)ZK_SHIFT_TABLES);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize((hipStream_t)0) != hipSuccess) {
+            hipFree(d);
+            return ZK_ERR_HIP;
+        }
+        bc.shift = d;
+        return ZK_OK;
+    }
+    return ZK_ERR_UNSUPPORTED;
+}
+
 template <class C>
 int bases_refresh_run(const BasesCopy& bc, uint64_t offset, uint64_t count, hipStream_t st) {
     if constexpr (has_f29<C>()) {
@@ -736,11 +757,17 @@ int ipa_collapse_run(DeviceCtx& dc, const BasesCopy& bc, uint64_t base_n, const 
         HIP_TRY(hipStreamSynchronize(st));
         return ZK_OK;
     }
-    int c = 2;                           // per output and window: T additions into the buckets + 2 per bucket to reduce them
+    // K = 4 over the handle's shift tables ([2^(64 k)] P in row k: every 255-bit weight is four 64-bit scalars over four points),
+    // K = 1 over the points alone.  Per output and window: K T additions into the buckets + 2 per bucket to reduce them; every
+    // chunk has ceil(chunk bits / c) windows, the top one narrower (K = 1: one chunk, the whole scalar plus the carry bit).
+    static_assert(Fr::BITS < 64 * ZK_SHIFT_TABLES, "the top chunk must absorb the last carry");
+    const uint32_t K = bc.shift && ipa_shift_tables_enabled() ? (uint32_t)ZK_SHIFT_TABLES : 1u;
+    const uint32_t chunk_bits = K > 1 ? 64u : (uint32_t)Fr::BITS + 1;
+    int c = 2;
     {
         uint64_t best = ~0ull;
         for (int cc = 2; cc <= 8; cc++) {
-            const uint64_t cost = ((uint64_t)T + (1ull << cc)) * (uint64_t)msm_windows<C>(cc);
+            const uint64_t cost = ((uint64_t)K * T + (1ull << cc)) * (uint64_t)((chunk_bits + cc - 1) / cc);
             if (cost < best) {
                 best = cost;
                 c = cc;
@@ -748,10 +775,11 @@ int ipa_collapse_run(DeviceCtx& dc, const BasesCopy& bc, uint64_t base_n, const 
         }
     }
     const uint32_t nbk = 1u << (c - 1);
-    const uint32_t nwin = (uint32_t)msm_windows<C>(c);
+    const uint32_t nwin = (chunk_bits + c - 1) / c;
+    const uint32_t E = K * T;            // entries per window at most
     StreamScratch* ss = nullptr;
     ZK_TRY(stream_scratch(dc, st, &ss));
-    const size_t list_words = (size_t)nwin * nbk + 1 + (size_t)nwin * T;
+    const size_t list_words = (size_t)nwin * nbk + 1 + (size_t)nwin * E;
     ZK_TRY(ws_get(ss->poly_a, (size_t)T * sizeof(Fe<Fr>) + list_words * 4 + 64));
     ZK_TRY(ws_get(ss->poly_b, (size_t)nwin * cnt * sizeof(XYZZ<CK>)));
     ZK_TRY(ws_get(ss->fb_tmp, (size_t)cnt * sizeof(XYZZ<C>)));
@@ -764,44 +792,48 @@ int ipa_collapse_run(DeviceCtx& dc, const BasesCopy& bc, uint64_t base_n, const 
     std::vector<Fe<Fr>> wt(T);
     HIP_TRY(hipMemcpyAsync(wt.data(), d_w, (size_t)T * sizeof(Fe<Fr>), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    // signed c-bit digits of every weight (the carry method of msm_digits_kernel), then the bucket lists of every window
-    auto bits = [&](const Fe<Fr>& x, int start) -> uint32_t {
+    // signed digits of every weight (the carry method of msm_digits_kernel; the carry runs on across the chunk boundaries, and the
+    // last chunk cannot carry out: the weights are below the modulus), then the bucket lists of every window
+    auto bits = [&](const Fe<Fr>& x, uint32_t start, uint32_t width) -> uint32_t {
         uint64_t v = 0;
-        const int idx = start >> 5, sh = start & 31;
-        if (idx < Fr::N) v = x.v[idx];
-        if (idx + 1 < Fr::N) v |= (uint64_t)x.v[idx + 1] << 32;
-        return (uint32_t)(v >> sh) & ((1u << c) - 1);
+        const uint32_t idx = start >> 5, sh = start & 31;
+        if (idx < (uint32_t)Fr::N) v = x.v[idx];
+        if (idx + 1 < (uint32_t)Fr::N) v |= (uint64_t)x.v[idx + 1] << 32;
+        return (uint32_t)(v >> sh) & ((1u << width) - 1);
     };
-    std::vector<int32_t> dig((size_t)nwin * T);
-    std::vector<uint32_t> off((size_t)nwin * nbk + 1, 0), ent((size_t)nwin * T);
+    std::vector<int32_t> dig((size_t)nwin * E);      // [window][chunk][t]
+    std::vector<uint32_t> off((size_t)nwin * nbk + 1, 0), ent((size_t)nwin * E);
     for (uint32_t t = 0; t < T; t++) {
         uint32_t carry = 0;
-        for (uint32_t w = 0; w < nwin; w++) {
-            const uint32_t raw = bits(wt[t], (int)(w * c)) + carry;
-            const bool neg = raw > nbk;
-            const uint32_t mag = neg ? (1u << c) - raw : raw;
-            carry = neg ? 1u : 0u;
-            dig[(size_t)w * T + t] = neg ? -(int32_t)mag : (int32_t)mag;
-            if (mag) off[(size_t)w * nbk + (mag - 1) + 1]++;
-        }
+        for (uint32_t k = 0; k < K; k++)
+            for (uint32_t w = 0; w < nwin; w++) {
+                const uint32_t width = (w + 1) * c <= chunk_bits ? (uint32_t)c : chunk_bits - w * c;
+                const uint32_t raw = bits(wt[t], k * chunk_bits + w * c, width) + carry;
+                const bool neg = raw > (1u << (width - 1));
+                const uint32_t mag = neg ? (1u << width) - raw : raw;
+                carry = neg ? 1u : 0u;
+                dig[((size_t)w * K + k) * T + t] = neg ? -(int32_t)mag : (int32_t)mag;
+                if (mag) off[(size_t)w * nbk + (mag - 1) + 1]++;
+            }
     }
     for (size_t k = 1; k < off.size(); k++) off[k] += off[k - 1];
     {
         std::vector<uint32_t> pos(off.begin(), off.end() - 1);
         for (uint32_t w = 0; w < nwin; w++)
-            for (uint32_t t = 0; t < T; t++) {
-                const int32_t d = dig[(size_t)w * T + t];
-                if (d == 0) continue;
-                const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
-                ent[pos[(size_t)w * nbk + (mag - 1)]++] = t | (d < 0 ? 0x80000000u : 0u);
-            }
+            for (uint32_t k = 0; k < K; k++)
+                for (uint32_t t = 0; t < T; t++) {
+                    const int32_t d = dig[((size_t)w * K + k) * T + t];
+                    if (d == 0) continue;
+                    const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
+                    ent[pos[(size_t)w * nbk + (mag - 1)]++] = t | (k << 28) | (d < 0 ? 0x80000000u : 0u);
+                }
     }
     HIP_TRY(hipMemcpyAsync(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_ent, ent.data(), ent.size() * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));   // the host vectors go out of scope below
     const uint64_t lanes = (uint64_t)nwin * cnt;
-    ZK_LAUNCH((ipa_collapse_window_kernel<CK>), (unsigned)((lanes + 63) / 64), 64, 0, st, (const StoredAffine<CK>*)bc.dev29,
-              (const uint32_t*)d_off, (const uint32_t*)d_ent, part, m, i0, cnt, nbk, nwin);
+    ZK_LAUNCH((ipa_collapse_window_kernel<CK>), (unsigned)((lanes + 63) / 64), 64, 0, st, (const StoredAffine<CK>*)(K > 1 ? bc.shift : bc.dev29),
+              (const uint32_t*)d_off, (const uint32_t*)d_ent, part, m, i0, cnt, nbk, nwin, (uint32_t)(K > 1 ? base_n : 0));
     ZK_LAUNCH((ipa_collapse_horner_kernel<C>), (cnt + 63) / 64, 64, 0, st, (const XYZZ<CK>*)part, tmp, cnt, (uint32_t)c, nwin);
     const uint64_t nl = ((uint64_t)cnt + FB_K - 1) / FB_K;
     ZK_LAUNCH((xyzz_batch_to_affine_kernel<C>), (unsigned)((nl + 63) / 64), 64, 0, st, (const XYZZ<C>*)tmp, g_out, cnt);

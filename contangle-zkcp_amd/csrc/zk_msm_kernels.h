@@ -1401,11 +1401,13 @@ __global__ void __launch_bounds__(256) ipa_gather_weights_kernel(const Fe<typena
     out[t] = x;
 }
 
-// list_off[w nbk + b] .. list_off[w nbk + b + 1]: the entries (t | sign << 31) whose digit in window w has magnitude b + 1
+// list_off[w nbk + b] .. list_off[w nbk + b + 1]: the entries (t | k << 28 | sign << 31) whose digit in window w has magnitude b + 1.
+// k > 0 only over a handle's shift tables (BasesCopy::shift, bases = [4][chunk_stride] points, [2^(64 k)] P_i in row k): the weights
+// are then cut into 64-bit chunks, window w of the kernel is window w of EVERY chunk, and chunk k of W_t selects row k of point t.
 template <class CK>
 __global__ void __launch_bounds__(64) ipa_collapse_window_kernel(const StoredAffine<CK>* __restrict__ bases, const uint32_t* __restrict__ list_off,
                                                                  const uint32_t* __restrict__ list_ent, XYZZ<CK>* __restrict__ out, uint32_t m,
-                                                                 uint32_t i0, uint32_t cnt, uint32_t nbk, uint32_t nwin) {
+                                                                 uint32_t i0, uint32_t cnt, uint32_t nbk, uint32_t nwin, uint32_t chunk_stride) {
     // outputs i0 .. i0 + cnt of the m survivors (a rank's share, or all of them); out is [window][cnt]
     const uint64_t gt = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t il = (uint32_t)(gt % cnt), w = (uint32_t)(gt / cnt);
@@ -1424,7 +1426,7 @@ __global__ void __launch_bounds__(64) ipa_collapse_window_kernel(const StoredAff
         for (uint32_t k = off[b]; k < e1; k++) {
             const uint32_t e = list_ent[k];
             Affine<CK> p;
-            load_base(p, bases, (e & 0x7fffffffu) * m + i);
+            load_base(p, bases, ((e >> 28) & 7u) * chunk_stride + (e & 0x0fffffffu) * m + i);
             aff_neg_if(p, (e >> 31) != 0);
             xyzz_add_mixed(bsum, p);
         }

@@ -19,7 +19,7 @@ from . import (Bases, ZkError, _check, _np64, _ptr, base_limbs, curve_id, field_
 
 PROVER_EXPORTS = ["zk_batch_invert_device", "zk_prefix_product_device", "zk_halo2_permutation_product_device",
                   "zk_halo2_lookup_product_device", "zk_halo2_permute_expression_pair_device", "zk_inner_product_device", "zk_vec_fold_device", "zk_ipa_fold_bases_device",
-                  "zk_expr_eval_device", "zk_ipa_virtual_scalars_device", "zk_ipa_update_weights_device", "zk_ipa_collapse_device", "zk_ipa_collapse_range_device", "zk_ipa_round_device",
+                  "zk_expr_eval_device", "zk_ipa_virtual_scalars_device", "zk_ipa_update_weights_device", "zk_ipa_collapse_device", "zk_ipa_collapse_range_device", "zk_ipa_round_device", "zk_bases_precompute_shifts", "zk_bases_shift_tables",
                   "zk_poly_eval_device", "zk_poly_eval_batch_device", "zk_vec_muladd_device", "zk_vec_muladd_to_device", "zk_kate_division_device", "zk_vec_powers_device", "zk_vec_fold_many_device",
                   "zk_ipa_fold_round_device", "zk_expr_eval_lazy_device", "zk_expr_configure", "zk_expr_specialised_source",
                   "zk_halo2_assembly_new", "zk_halo2_assembly_copy", "zk_halo2_assembly_mapping", "zk_halo2_assembly_free",
@@ -341,6 +341,8 @@ def _plib():
     lib.zk_ipa_update_weights_device.argtypes = [i32, vp, u64, u64, vp, vp]
     lib.zk_ipa_collapse_device.argtypes = [i32, u64, vp, u64, u64, vp, vp]
     lib.zk_ipa_collapse_range_device.argtypes = [i32, u64, vp, u64, u64, u64, u64, vp, vp]
+    lib.zk_bases_precompute_shifts.argtypes = [i32, u64]
+    lib.zk_bases_shift_tables.argtypes = [u64, ctypes.POINTER(u64)]
     lib.zk_ipa_round_device.argtypes = [i32, u64, vp, vp, vp, u64, u64, vp, vp, vp, vp]
     lib.zk_poly_eval_device.argtypes = [i32, vp, u64, vp, vp, vp]
     lib.zk_vec_muladd_device.argtypes = [i32, vp, vp, u64, vp, vp]

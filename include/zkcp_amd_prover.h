@@ -317,6 +317,19 @@ int zk_ipa_collapse_device(zk_curve_t c, uint64_t bases_handle, const void *w_de
 int zk_ipa_collapse_range_device(zk_curve_t c, uint64_t bases_handle, const void *w_dev, uint64_t m0, uint64_t cur, uint64_t first,
                                  uint64_t count, void *g_out_range_dev, void *hip_stream);
 
+/* Shift tables for the collapse above: [2^64] G_i, [2^128] G_i, [2^192] G_i beside the handle's points (3 x the lazy-limb copy more:
+ * 192 MiB for a 2^20-point Pasta key), so that every 255-bit weight is four 64-bit scalars over four points -- 11 six-bit windows
+ * instead of 52 five-bit ones, and 60 doublings per survivor instead of 255.  The generators of poly/commitment/prover.rs
+ * create_proof are Params::g, the same from proof to proof: call this once where the key is loaded (poly/commitment.rs
+ * Params::new / Params::read).  One inversion per table entry; synchronises.  Without the call the library builds the tables by
+ * itself at the SECOND collapse over a handle of at least 2^16 points (the first runs without them, so does every collapse over a
+ * smaller or short-lived handle, and so does everything when the allocation fails).  zk_bases_refresh drops the tables: call
+ * again after rewriting the points.  ZK_IPA_SHIFT_TABLES=0 in the environment (read once) turns tables off: nothing is built,
+ * here or automatically.  The collapse returns canonical affine points: the same bits with or without tables. */
+int zk_bases_precompute_shifts(zk_curve_t c, uint64_t bases_handle);
+/* *present = 1 when every device's copy of the handle holds shift tables at the moment, else 0 */
+int zk_bases_shift_tables(uint64_t bases_handle, uint64_t *present);
+
 /* ---- halo2 verification (halo2_proofs 0.2 poly/commitment/verifier.rs verify_proof / Guard, poly/commitment/msm.rs MSM) ----
  * The opening check ends in ONE multi-scalar multiplication over the whole SRS, whose scalars are compute_s of the k round
  * challenges.  That vector is built here; the MSM is zk_msm_device over the resident g with scalars_are_montgomery = 1, the few

@@ -313,6 +313,8 @@ extern "C" {
                                s_dev: *mut c_void, lr_out_host: *mut c_void, v_out_mont_host: *mut c_void, hip_stream: *mut c_void) -> c_int;
     pub fn zk_ipa_collapse_device(c: c_int, bases_handle: u64, w_dev: *const c_void, m0: u64, cur: u64, g_out_affine_dev: *mut c_void,
                                   hip_stream: *mut c_void) -> c_int;
+    pub fn zk_bases_precompute_shifts(c: c_int, bases_handle: u64) -> c_int;
+    pub fn zk_bases_shift_tables(bases_handle: u64, present: *mut u64) -> c_int;
     pub fn zk_expr_eval_device(f: c_int, program_host: *const zk_expr_op, n_ops: u32, columns_dev: *const *const c_void, n_columns: u32,
                                consts_mont_host: *const c_void, n_consts: u32, log_n_ext: u32, rot_scale: u32, out_dev: *mut c_void,
                                hip_stream: *mut c_void) -> c_int;
