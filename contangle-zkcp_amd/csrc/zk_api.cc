@@ -928,21 +928,10 @@ static int batch_on_device(DeviceCtx& dc, zk_curve_t c, const BasesEntry* be, co
     }
     // Up to 4 scalar vectors go into ONE job: their windows are simply more windows of the same sort / accumulate / reduce
     // launches (one persistent accumulate launch without a drain per MSM, the latency-bound reduction steps once per job).
-    // The bound is the (window, range) region count the sort kernels index: 4096.  Job k runs on side stream k mod 2; at most
+    // How many is the launch plan's answer (msm_plan_batch, zk_msm_plan.h).  Job k runs on side stream k mod 2; at most
     // ZK_MAX_JOBS - 1 in flight, collected in order.
     uint32_t per_job = 1;
-    {
-        int cw = 0, nwin = 0;
-        CURVE_SWITCH(c, cw = msm_pick_c(n, tu.window_bits, tu.precomputed); nwin = msm_windows<C>(cw));
-        const int nwj = (tu.w0 == 0 && tu.w1 == 0) ? nwin : tu.w1 - tu.w0;
-        const uint32_t nbk = 1u << (cw - 1), nranges = nbk > 512 ? nbk / 512 : 1;
-        // (the one-bucket-set form: one window of at most 1024 ranges per vector, whatever c)
-        const uint32_t regions = tu.precomputed ? (nranges > 1024 ? nranges : 1024u) : (uint32_t)(nwj > 0 ? nwj : 1) * nranges;
-        per_job = 4096 / regions;
-        if (per_job > 4) per_job = 4;
-        if (per_job < 1) per_job = 1;
-        if ((uint64_t)n * (uint64_t)(nwj > 0 ? nwj : 1) * per_job >= (1ull << 32)) per_job = 1;   // entry positions are u32
-    }
+    CURVE_SWITCH(c, per_job = msm_batch_size<C>(be->per_dev[dc.index], n, tu, dc.num_cus));
     struct Flight {
         MsmJob* job;
         uint32_t first, size;

@@ -22,6 +22,7 @@
 
 #include "zk_rt.h"
 #include "zk_curve.h"
+#include "zk_msm_plan.h"
 
 namespace zk {
 
@@ -78,24 +79,6 @@ struct TwEntry {
     void* dev;
     size_t bytes;
     uint64_t stamp;
-};
-
-// resolved MSM plan knobs (zk_msm_opts; 0 / negative = choose automatically)
-struct MsmTuning {
-    int window_bits = 0, w0 = 0, w1 = 0;
-    int split_log = -1;
-    uint32_t slice_len = 0;
-    uint32_t big_thresh = 0;
-    int limb_bits = 0;        // 32 forces the saturated path
-    int waves = 0;
-    int window_group = 0;     // windows per group of a large single MSM (0 = automatic)
-    bool no_hot_help = false;
-    bool slice_reduce = false;   // the round-1 bucket reduction (slices + multiplier) instead of row / column sums
-    bool device_partials = false;   // ZK_MSM_FLAG_DEVICE_PARTIALS: partial sums converted on the device, checked against the host's conversion
-    bool precomputed = false;    // ONE bucket set over the handle's precomputed window multiples (ZK_MSM_FLAG_PRECOMPUTED)
-    uint64_t base_offset = 0;
-    uint32_t batch = 1;          // internal (zk_msm_batch_device): scalar vectors summed by ONE job
-    uint64_t batch_stride = 0;   // elements between them
 };
 
 // One MSM in flight: its own device workspaces (so two jobs on two streams never share a buffer), a pinned host buffer

@@ -5,6 +5,9 @@ namespace zk {
 // enqueue the device work of one MSM on job.stream; the result is produced by job.finish after the job's last event
 template <class C>
 int msm_enqueue(MsmJob& job, const BasesCopy& bc, const Fe<typename C::Fr>* d_scalars, uint64_t n, int mont, const MsmTuning& tu);
+// scalar vectors per job of zk_msm_batch_device: the largest batch the launch plan accepts for this MSM (msm_plan_batch)
+template <class C>
+uint32_t msm_batch_size(const BasesCopy& bc, uint64_t n, const MsmTuning& tu, int num_cus);
 template <class C>
 int bases_prepare_run(BasesCopy& bc, uint64_t n);   // build the resident lazy-limb copy
 template <class C>

@@ -2,6 +2,7 @@
 #include "zk_msm.inl"
 namespace zk {
 template int msm_enqueue<ZK_CURVE>(MsmJob&, const BasesCopy&, const Fe<ZK_CURVE::Fr>*, uint64_t, int, const MsmTuning&);
+template uint32_t msm_batch_size<ZK_CURVE>(const BasesCopy&, uint64_t, const MsmTuning&, int);
 template int bases_prepare_run<ZK_CURVE>(BasesCopy&, uint64_t);
 template int bases_refresh_run<ZK_CURVE>(const BasesCopy&, uint64_t, uint64_t, hipStream_t);
 template int fixed_base_run<ZK_CURVE>(const Fe<ZK_CURVE::Fr>*, uint64_t, Affine<ZK_CURVE>*, hipStream_t);

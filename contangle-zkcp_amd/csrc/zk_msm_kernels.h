@@ -13,6 +13,8 @@
 #include "zk_curve.h"
 #include "zk_curve29.h"
 #include "zk_glv_params.h"
+#include "zk_msm_plan.h"
+// (zk_msm_plan.h: MsmShape, MsmAxes, MsmQueue, MsmSeg and the MSM_* constants, shared with the host's launch plan)
 
 namespace zk {
 
@@ -36,25 +38,6 @@ namespace zk {
 // of ranges -- the first version had each (window, range) workgroup filter the whole digit row of its window (16 x
 // redundant at c = 16) and scatter 4-byte stores across its region.
 // ------------------------------------------------------------------------------------------
-struct MsmShape {
-    uint32_t n;
-    int c;            // window bits (<= 16)
-    int w0, nw;       // this call accumulates windows [w0, w0 + nw) of the scalar (window-range sharding)
-    uint32_t nbk;     // buckets per window = 2^(c-1)
-    uint32_t rb;      // buckets per range (power of two, <= 512: a region of the sorted array should fit the LDS of its sort workgroup)
-    uint32_t nranges; // ranges per window = nbk / rb
-    int mont;         // scalars arrive in Montgomery form (halo2) rather than canonical (ark BigInt)
-    uint32_t big_thresh;  // buckets longer than this take the cooperative path
-    int split_log;        // every bucket's entry list is cut into 2^split_log pieces summed by different lanes (msm_combine_sub_kernel adds them)
-    uint32_t sblk;        // scalars per workgroup of the digit / stage kernels: MSM_SBLK, less for small inputs (>= 64 workgroups)
-    uint32_t batch;       // scalar vectors summed over the same bases by this job; nw = batch * nwb windows in all, window-major per vector
-    int nwb;              // windows per scalar vector
-    uint64_t batch_stride;   // elements between the scalar vectors
-    uint32_t seg;         // entries per cooperative segment of an oversized bucket (power of two in [128, MSM_SEG_MAX], from n: msm_seg_len)
-    uint32_t pre_n;       // precomputed-table form (ZK_MSM_FLAG_PRECOMPUTED): the real point count; n = pre_w * pre_n table entries,
-    uint32_t pre_w;       // ONE bucket set (nwb = 1): entry w * pre_n + i = the digit of scalar i in window w, point [2^(c w)] P_i
-};
-
 template <int N>
 __device__ __forceinline__ uint32_t word_at(const uint32_t (&s)[N], int idx) {
     uint32_t v = 0;
@@ -69,9 +52,6 @@ __device__ __forceinline__ uint32_t bits_at(const uint32_t (&s)[N], int start, i
     v |= (uint64_t)word_at<N>(s, idx + 1) << 32;  // idx+1 == N selects 0
     return (uint32_t)(v >> off) & ((1u << c) - 1);
 }
-
-constexpr uint32_t MSM_RANGE = 512;   // buckets per (window, range) region of the sort
-constexpr uint32_t MSM_SBLK = 4096;   // scalars per workgroup of the digit / stage kernels (1024 lanes x 4) at full size: MsmShape::sblk
 
 // u16 digit code: two's complement of the signed digit; positive magnitudes reach 2^15 (0x8000),
 // negative ones only 2^15 - 1, so the code is unambiguous:  neg <=> code > 0x8000.
@@ -325,10 +305,6 @@ __global__ void __launch_bounds__(1024) msm_stage_kernel(const DT* __restrict__ 
 }
 
 constexpr uint32_t MSM_HOT_UNROLL = 8;   // entries per lane and iteration in the hot-region loops of the sort kernel
-
-// ---- hot regions (far above the mean: a skewed witness) are histogrammed and scattered by many workgroups ----
-constexpr uint32_t MSM_HOT_MAX = 8;       // hot regions served this way (the rest stay with their own sort workgroup)
-constexpr uint32_t MSM_HOT_SLICES = 32;   // workgroups per hot region at most (n / 65536 of them for smaller inputs)
 
 // one workgroup: hot_flag[r] = 1 + rank for the first MSM_HOT_MAX regions with more than chunk_limit entries (0 otherwise),
 // hot_list[0] = their number, hot_list[1 + k] = the region of rank k.  nreg <= 1024.
@@ -587,33 +563,13 @@ __global__ void __launch_bounds__(1024) msm_sort_kernel(const uint32_t* __restri
 // (longest-processing-time order, so the SIMDs finish together).  Task t = (rank r, range g): lane l sums
 // bucket order[g*rb + 64 r + l].  Buckets longer than sh.big_thresh (a few times the mean length: skewed
 // witnesses, e.g. the 25% of unit scalars of a Groth16 assignment) are not summed by one lane: they are cut
-// into segments of sh.seg entries appended to `seg_list` for msm_accumulate_big_kernel.
-// Entries per cooperative segment (one wave: len / 64 additions per lane + a 6-level tree).  The worst oversized bucket of a
-// Groth16 assignment holds the unit scalars, a quarter of all entries: with 2048-entry segments a 2^20-point MSM cuts it into
-// 128 segments -- 128 waves on 1024 SIMDs, each doing 38 dependent additions (1.35 ms per G2 launch in round 2).  The length
-// now follows n so that such a bucket yields ~1024 segments: n / 4096, at least 128 (below that the tree dominates).
-constexpr uint32_t MSM_SEG_MAX = 2048;
-inline uint32_t msm_seg_len(uint64_t n) {
-    uint32_t s = 128;
-    while (s < MSM_SEG_MAX && (uint64_t)s * 4096 < n) s <<= 1;
-    return s;
-}
+// into segments of sh.seg entries (msm_seg_len, zk_msm_plan.h) appended to `seg_list` for msm_accumulate_big_kernel.
 
 // lanes per workgroup of the LDS tree kernels: 256 XYZZ points must fit the 64 KiB static LDS limit (G2: 384 B each)
 template <class C>
 constexpr uint32_t tree_lanes() {
     return sizeof(XYZZ<C>) * 256 <= 48 * 1024 ? 256u : 128u;
 }
-
-struct MsmQueue {          // device-side control words, zeroed before every MSM
-    uint32_t head;         // next task
-    uint32_t nseg;         // segments appended
-    uint32_t nbig;         // big buckets appended
-    uint32_t pad;
-};
-struct MsmSeg {
-    uint32_t bucket, start, len, big_index;
-};
 
 // How the bases of a kernel view are kept in HBM.  The saturated views read the points as uploaded.  The lazy-limb views
 // keep x R' mod p (a value below 2p) PACKED in the caller's 32-bit words -- 64 B per G1 point (96 B BLS12-381), 128 / 192 B on
@@ -674,10 +630,6 @@ __device__ __forceinline__ void accumulate_slice(XYZZ<C>& acc, const StoredAffin
 #ifndef ZK_ACC_WAVES_9
 #define ZK_ACC_WAVES_9 4
 #endif
-constexpr uint32_t MSM_BATCH = 64;
-// Visiting order: rank-major over the per-range size-sorted bucket lists, MSM_RANKW buckets of a range at a time.  The
-// narrower the rank, the closer the order is to globally largest-first (512-bucket ranges: 32 ranks).
-constexpr uint32_t MSM_RANKW = 16;
 
 // resident waves per SIMD the accumulate kernel is compiled for: the 9-limb lazy form needs 134 VGPRs unconstrained (3 waves);
 // held to 128 (8 dwords of scratch) a fourth wave fits -- issue efficiency grows with the number of resident waves
@@ -1042,16 +994,6 @@ __global__ void __launch_bounds__(256) msm_sum_kernel(const XYZZ<C>* __restrict_
 //   host                       axis total = sum_u W_u + TL * sum_u u S_u ; window = 2^lc * rows + columns ; Horner
 // Each kernel has ONE addition site (instruction cache: see msm_reduce_kernel).
 // ------------------------------------------------------------------------------------------
-struct MsmAxes {
-    uint32_t nbk;        // buckets per window = rows * cols
-    uint32_t nw;         // windows
-    uint32_t log_cols;   // C = 2^log_cols, R = nbk / C  (R <= C)
-    uint32_t k_row, k_col;   // buckets per lane in the partials kernel (powers of two, k_row <= C, k_col <= R)
-    // derived
-    uint32_t rows, cols, p_row, p_col;   // partials per row = C / k_row, per column = R / k_col
-    uint32_t row_lanes, col_lanes;       // nw * rows * p_row, nw * cols * p_col
-};
-
 template <class C>
 __global__ void __launch_bounds__(64) msm_axis_partials_kernel(const XYZZ<C>* __restrict__ buckets, XYZZ<C>* __restrict__ part, MsmAxes A) {
     const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
