@@ -377,3 +377,4 @@ int witness_map_run(DeviceCtx& dc, int field, Fe<F>* a, Fe<F>* b, Fe<F>* c, uint
 #include "zk_keygen.inl"
 #include "zk_ipa_verify.inl"
 #include "zk_mock.inl"
+#include "zk_poseidon.inl"

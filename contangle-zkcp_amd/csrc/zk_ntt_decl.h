@@ -117,4 +117,21 @@ int mock_lookup_run(DeviceCtx& dc, const Fe<F>* A, const uint8_t* a_status, cons
                     hipStream_t st);
 template <class F>
 int witness_map_run(DeviceCtx& dc, int field, Fe<F>* a, Fe<F>* b, Fe<F>* c, uint32_t logm, hipStream_t st);
+// Poseidon, the Merkle tree over it and the ElGamal stream (zk_poseidon.inl).  tbl: [ark | mds | init], host memory for the *_host_run
+// twins (no device, no zk_init), the handle's device table otherwise.
+struct PoseidonShape;
+template <class F>
+int poseidon_permute_host_run(const PoseidonShape& sh, const Fe<F>* tbl, Fe<F>* states, uint64_t count);
+template <class F>
+int poseidon_hash_host_run(const PoseidonShape& sh, const Fe<F>* tbl, const Fe<F>* in, uint32_t arity, uint64_t count, Fe<F>* out);
+template <class F>
+int poseidon_permute_run(const PoseidonShape& sh, const Fe<F>* tbl, Fe<F>* states, uint64_t count, hipStream_t st);
+template <class F>
+int poseidon_hash_run(const PoseidonShape& sh, const Fe<F>* tbl, const Fe<F>* in, uint32_t arity, uint64_t count, Fe<F>* out, hipStream_t st);
+template <class F>
+int poseidon_tree_run(const PoseidonShape& sh, const Fe<F>* tbl, const Fe<F>* leaves, uint32_t leaf_arity, uint32_t log_n, Fe<F>* nodes, hipStream_t st);
+template <class F>
+int merkle_paths_run(const Fe<F>* nodes, uint32_t log_n, const uint64_t* idx_host, uint64_t count, Fe<F>* out, hipStream_t st);
+template <class F>
+int vec_add_scalar_run(Fe<F>* out, const Fe<F>* a, uint64_t n, const Fe<F>& s, hipStream_t st);
 }  // namespace zk

@@ -49,4 +49,11 @@ template int mock_eval_run<ZK_FIELD>(DeviceCtx&, uint32_t, const zk_expr_op*, co
 template int mock_failures_run<ZK_FIELD>(DeviceCtx&, const uint8_t*, uint64_t, uint64_t, uint64_t*, uint8_t*, uint64_t*, hipStream_t);
 template int mock_permutation_run<ZK_FIELD>(DeviceCtx&, uint32_t, uint32_t, const void* const*, const uint64_t*, const uint64_t*, uint8_t*, int*, hipStream_t);
 template int mock_lookup_run<ZK_FIELD>(DeviceCtx&, const Fe<ZK_FIELD>*, const uint8_t*, const Fe<ZK_FIELD>*, const uint8_t*, uint32_t, uint8_t*, hipStream_t);
+template int poseidon_permute_host_run<ZK_FIELD>(const PoseidonShape&, const Fe<ZK_FIELD>*, Fe<ZK_FIELD>*, uint64_t);
+template int poseidon_hash_host_run<ZK_FIELD>(const PoseidonShape&, const Fe<ZK_FIELD>*, const Fe<ZK_FIELD>*, uint32_t, uint64_t, Fe<ZK_FIELD>*);
+template int poseidon_permute_run<ZK_FIELD>(const PoseidonShape&, const Fe<ZK_FIELD>*, Fe<ZK_FIELD>*, uint64_t, hipStream_t);
+template int poseidon_hash_run<ZK_FIELD>(const PoseidonShape&, const Fe<ZK_FIELD>*, const Fe<ZK_FIELD>*, uint32_t, uint64_t, Fe<ZK_FIELD>*, hipStream_t);
+template int poseidon_tree_run<ZK_FIELD>(const PoseidonShape&, const Fe<ZK_FIELD>*, const Fe<ZK_FIELD>*, uint32_t, uint32_t, Fe<ZK_FIELD>*, hipStream_t);
+template int merkle_paths_run<ZK_FIELD>(const Fe<ZK_FIELD>*, uint32_t, const uint64_t*, uint64_t, Fe<ZK_FIELD>*, hipStream_t);
+template int vec_add_scalar_run<ZK_FIELD>(Fe<ZK_FIELD>*, const Fe<ZK_FIELD>*, uint64_t, const Fe<ZK_FIELD>&, hipStream_t);
 }  // namespace zk

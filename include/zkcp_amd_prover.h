@@ -446,6 +446,45 @@ int zk_expr_configure(int jit_mode);
 int zk_expr_specialised_source(zk_field_t f, const zk_expr_op *program_host, uint32_t n_ops, uint32_t n_columns, uint32_t n_consts, char *out,
                                uint64_t cap, uint64_t *len_out);
 
+/* ---- Poseidon, the Merkle tree over it, and the ElGamal c2 stream ("Poseidon") ----
+ * The reference's seller path outside Groth16::prove: EncryptCircuit::encrypt hashes the shared point and adds the digest to the whole
+ * plaintext; SampleEntries::new builds a Poseidon Merkle tree over the ciphertext and opens one path.  The library holds no parameter
+ * set: the caller states one and gets a handle.
+ *   permutation   round i of full_rounds + partial_rounds: s[j] += ark[i][j]; s[j] = s[j]^alpha for every j in the first and last
+ *                 full_rounds / 2 rounds, for j = 0 only in between; s = mds s
+ *   hash          of `arity` elements: s = init; the elements are added into s[rate_offset ..), `rate` at a time, a permutation after
+ *                 every block (the last included, none extra after a full one); the digest is s[rate_offset].
+ *                 ark-sponge 0.3 (PoseidonSponge, CRH, TwoToOneCRH at width 3): rate 2, rate_offset 1, init NULL.
+ *                 halo2_gadgets ConstantLength<L> at width 3: rate 2, rate_offset 0, init = (0, 0, L * 2^64).
+ * Every element is 4 u64 words, Montgomery; device pointers are 16-B aligned.  ark_mont_host: (full_rounds + partial_rounds) x width,
+ * mds_mont_host: width x width (row-major), init_mont_host: width elements or NULL for zeros, all canonical.
+ * ZK_ERR_INVALID_ARG, before anything is launched: a null pointer; width outside 2 .. 5; rate = 0 or rate_offset + rate > width; odd
+ * full_rounds; full_rounds + partial_rounds = 0 or > 256; alpha = 0; a constant >= p; arity = 0 or > 64; log_n = 0 or > 30; a path
+ * index >= 2^log_n; an output overlapping an input.  ZK_ERR_BAD_HANDLE: a handle that was freed or never made.  The library stays
+ * usable after every refusal.  create / free / the two *_host entries (the same arithmetic on the CPU's 64-bit multiplier, one
+ * thread) need neither a device nor zk_init; the *_device entries return ZK_ERR_NOT_INITIALIZED without one, enqueue on hip_stream
+ * and do not synchronise it.  A handle's table goes to a device once, at its first *_device call there; handles outlive zk_shutdown. */
+int zk_poseidon_create(zk_field_t f, uint32_t width, uint32_t rate, uint32_t rate_offset, uint32_t full_rounds, uint32_t partial_rounds,
+                       uint64_t alpha, const void *ark_mont_host, const void *mds_mont_host, const void *init_mont_host, uint64_t *handle_out);
+int zk_poseidon_free(uint64_t handle);
+/* count states of `width` elements each, permuted in place */
+int zk_poseidon_permute_host(uint64_t handle, void *states_mont_host, uint64_t count);
+int zk_poseidon_permute_device(uint64_t handle, void *states_dev, uint64_t count, void *hip_stream);
+/* out[i] = hash of in[i * arity .. (i + 1) * arity), i < count.  Inputs must be canonical (< p), as in every vector entry. */
+int zk_poseidon_hash_host(uint64_t handle, const void *in_mont_host, uint32_t arity, uint64_t count, void *out_mont_host);
+int zk_poseidon_hash_device(uint64_t handle, const void *in_dev, uint32_t arity, uint64_t count, void *out_dev, void *hip_stream);
+/* ark MerkleTree::new over n = 2^log_n leaves of leaf_arity elements each (leaf and two-to-one parameters the same, identity digest
+ * converter).  nodes_dev: 2n - 1 elements.  Level 0 = the leaf digests at nodes[0 .. n); node i of level j + 1 = hash of
+ * (level_j[2i], level_j[2i + 1]); level j starts at 2n - 2^(log_n - j + 1); the root is nodes[2n - 2].  (Upstream's heap order is not
+ * mirrored.)  One launch for the leaves, one per level of more than 256 nodes, one for all the levels above: 13 for 2^20 leaves. */
+int zk_poseidon_merkle_tree_device(uint64_t handle, const void *leaves_dev, uint32_t leaf_arity, uint32_t log_n, void *nodes_dev, void *hip_stream);
+/* out[c * log_n + j] = level_j[(indices[c] >> j) ^ 1], j < log_n: the siblings of leaf indices[c], bottom-up.  The index list is read
+ * before the call returns. */
+int zk_merkle_paths_device(zk_field_t f, const void *nodes_dev, uint32_t log_n, const uint64_t *indices_host, uint64_t count, void *out_dev,
+                           void *hip_stream);
+/* out[i] = a[i] + s, i < n (encrypt: s = dh; decrypt: s = -dh).  out_dev may be a_dev itself; any other overlap is refused. */
+int zk_vec_add_scalar_device(zk_field_t f, void *out_dev, const void *a_dev, uint64_t n, const void *scalar_mont_host, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

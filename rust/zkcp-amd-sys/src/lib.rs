@@ -284,6 +284,19 @@ extern "C" {
                                             mapping_dev: *const c_void, status_out_dev: *mut u8, hip_stream: *mut c_void) -> c_int;
     pub fn zk_halo2_mock_failures_device(status_dev: *const u8, n_status: u64, cap: u64, positions_out_host: *mut u64, kinds_out_host: *mut u8,
                                          total_out_host: *mut u64, hip_stream: *mut c_void) -> c_int;
+    pub fn zk_poseidon_create(f: c_int, width: u32, rate: u32, rate_offset: u32, full_rounds: u32, partial_rounds: u32, alpha: u64,
+                              ark_mont_host: *const c_void, mds_mont_host: *const c_void, init_mont_host: *const c_void, handle_out: *mut u64) -> c_int;
+    pub fn zk_poseidon_free(handle: u64) -> c_int;
+    pub fn zk_poseidon_permute_host(handle: u64, states_mont_host: *mut c_void, count: u64) -> c_int;
+    pub fn zk_poseidon_permute_device(handle: u64, states_dev: *mut c_void, count: u64, hip_stream: *mut c_void) -> c_int;
+    pub fn zk_poseidon_hash_host(handle: u64, in_mont_host: *const c_void, arity: u32, count: u64, out_mont_host: *mut c_void) -> c_int;
+    pub fn zk_poseidon_hash_device(handle: u64, in_dev: *const c_void, arity: u32, count: u64, out_dev: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn zk_poseidon_merkle_tree_device(handle: u64, leaves_dev: *const c_void, leaf_arity: u32, log_n: u32, nodes_dev: *mut c_void,
+                                          hip_stream: *mut c_void) -> c_int;
+    pub fn zk_merkle_paths_device(f: c_int, nodes_dev: *const c_void, log_n: u32, indices_host: *const u64, count: u64, out_dev: *mut c_void,
+                                  hip_stream: *mut c_void) -> c_int;
+    pub fn zk_vec_add_scalar_device(f: c_int, out_dev: *mut c_void, a_dev: *const c_void, n: u64, scalar_mont_host: *const c_void,
+                                    hip_stream: *mut c_void) -> c_int;
     pub fn zk_inner_product_device(f: c_int, a_dev: *const c_void, b_dev: *const c_void, n: u64, out_mont_host: *mut c_void,
                                    hip_stream: *mut c_void) -> c_int;
     pub fn zk_poly_eval_device(f: c_int, coeffs_dev: *const c_void, n: u64, x_mont_host: *const c_void, out_mont_host: *mut c_void,
