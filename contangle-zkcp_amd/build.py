@@ -18,7 +18,9 @@ PROBE_LIB = os.path.join(EMU_DIR, "libzk_field_probe.so")
 CURVES = ["Pallas", "Vesta", "Bn254G1", "Bls381G1", "Bn254G2", "Bls381G2"]
 FIELDS = ["PallasFp", "PallasFq", "Bn254Fr", "Bls381Fr"]
 # (source, extra define, object tag)
-UNITS = [("zk_api.cc", None, "api"), ("zk_wire.cc", None, "wire"), ("zk_pairing.cc", None, "pairing")] + \
+UNITS = [("zk_runtime.cc", None, "runtime")] + \
+        [("zk_api_%s.cc" % s, None, "api_" + s) for s in ("bases", "msm", "field", "groth16", "halo2", "poseidon")] + \
+        [("zk_wire.cc", None, "wire"), ("zk_pairing.cc", None, "pairing")] + \
         [("zk_msm_inst.cc", "ZK_CURVE=" + c, "msm_" + c) for c in CURVES] + \
         [("zk_ntt_inst.cc", "ZK_FIELD=" + f, "ntt_" + f) for f in FIELDS]
 
@@ -82,7 +84,7 @@ def build_hip(force=False, verbose=False, jobs=None):
     deps = _deps()
     if not force and not _newer(LIB, deps):
         return LIB
-    jobs = jobs or min(len(UNITS), os.cpu_count() or 4)
+    jobs = jobs or min(len(UNITS), 16, os.cpu_count() or 4)
     objdir = os.path.join(PKG, "build", "hip")
     if force:
         shutil.rmtree(objdir, ignore_errors=True)
@@ -100,7 +102,7 @@ def build_emu(force=False, verbose=False, sanitize=False, jobs=None):
     deps = _deps() + [os.path.join(EMU_DIR, "emu_hip.h"), os.path.join(EMU_DIR, "emu_hip.cpp")]
     if not force and not _newer(out, deps):
         return out
-    jobs = jobs or min(len(UNITS), os.cpu_count() or 4)
+    jobs = jobs or min(len(UNITS), 16, os.cpu_count() or 4)
     objdir = os.path.join(PKG, "build", "emu_ubsan" if sanitize else "emu")
     if force:
         shutil.rmtree(objdir, ignore_errors=True)
@@ -130,7 +132,7 @@ def build_probe(force=False, verbose=False, jobs=None):
     probe_src = [os.path.join(EMU_DIR, "field_probe.hip"), os.path.join(EMU_DIR, "field_ops.h")]
     if not force and not _newer(PROBE_LIB, _deps() + probe_src):
         return PROBE_LIB
-    jobs = jobs or min(len(PROBE_UNITS), os.cpu_count() or 4)
+    jobs = jobs or min(len(PROBE_UNITS), 16, os.cpu_count() or 4)
     objdir = os.path.join(PKG, "build", "probe")
     if force:
         shutil.rmtree(objdir, ignore_errors=True)

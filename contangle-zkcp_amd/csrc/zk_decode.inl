@@ -7,8 +7,8 @@ namespace zk {
 // the stream's fb_tmp behind the status word; one copy up, one launch, one word back; synchronises `st` once, to read that word.
 // A rejected point gives ZK_ERR_INVALID_ARG with the smallest rejected index and its reason; d_out is then unspecified.
 template <class C>
-int points_decode_checked_run(DeviceCtx& dc, const uint8_t* in_host, uint64_t n, int compressed, Affine<C>* d_out, uint64_t* first_bad,
-                              uint64_t* reason, hipStream_t st) {
+int CurveLaunch<C>::points_decode_checked_run(DeviceCtx& dc, const uint8_t* in_host, uint64_t n, int compressed, Affine<C>* d_out, uint64_t* first_bad,
+                                              uint64_t* reason, hipStream_t st) {
     if constexpr (ArkG1<C>::HAS) {
         using Fq = typename C::Fq;
         if (n >= (1ull << 31)) return ZK_ERR_INVALID_ARG;

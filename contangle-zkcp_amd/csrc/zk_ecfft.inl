@@ -17,7 +17,7 @@ bool ecfft_omega_ok(const Fe<F>& omega, uint32_t logn) {
 // dst[i] = sum_j [omega^(i j)] src[j] (times n^-1 when scale), n = 2^logn; affine in, canonical affine out; src == dst allowed.
 // Workspaces: the stream's fb_tmp (n XYZZ points) and fb_table (n / 2 split twiddles).  Does not synchronise.
 template <class C>
-int ntt_points_run(DeviceCtx& dc, const Affine<C>* src, Affine<C>* dst, uint32_t logn, const Fe<typename C::Fr>& omega, int scale, hipStream_t st) {
+int CurveLaunch<C>::ntt_points_run(DeviceCtx& dc, const Affine<C>* src, Affine<C>* dst, uint32_t logn, const Fe<typename C::Fr>& omega, int scale, hipStream_t st) {
     if constexpr (Glv<C>::HAS) {
         using Fr = typename C::Fr;
         if (logn > ECFFT_MAX_LOG || !ecfft_omega_ok<Fr>(omega, logn)) return ZK_ERR_INVALID_ARG;
@@ -63,7 +63,7 @@ int ntt_points_run(DeviceCtx& dc, const Affine<C>* src, Affine<C>* dst, uint32_t
 
 // host points, in place: Jacobian (x, y, z) in, (x, y, 1) or (0, 1, 0) out.  Synchronises the null stream.
 template <class C>
-int ntt_points_host_run(DeviceCtx& dc, void* jac_host, uint32_t logn, const Fe<typename C::Fr>& omega, int scale) {
+int CurveLaunch<C>::ntt_points_host_run(DeviceCtx& dc, void* jac_host, uint32_t logn, const Fe<typename C::Fr>& omega, int scale) {
     if constexpr (Glv<C>::HAS) {
         if (logn > ECFFT_MAX_LOG || !ecfft_omega_ok<typename C::Fr>(omega, logn)) return ZK_ERR_INVALID_ARG;
         const uint32_t n = 1u << logn;
@@ -86,7 +86,7 @@ int ntt_points_host_run(DeviceCtx& dc, void* jac_host, uint32_t logn, const Fe<t
         ZK_LAUNCH((ecfft_jac_to_xyzz_kernel<C>), (n + 255) / 256, 256, 0, st, (const Jacobian<C>*)d_jac, (XYZZ<C>*)ss->fb_tmp.p, n);
         const uint32_t lanes = (n + FB_K - 1) / FB_K;
         ZK_LAUNCH((xyzz_batch_to_affine_kernel<C>), (lanes + 63) / 64, 64, 0, st, (const XYZZ<C>*)ss->fb_tmp.p, (Affine<C>*)d_aff, n);
-        const int status = ntt_points_run<C>(dc, (const Affine<C>*)d_aff, (Affine<C>*)d_aff, logn, omega, scale, st);
+        const int status = ntt_points_run(dc, (const Affine<C>*)d_aff, (Affine<C>*)d_aff, logn, omega, scale, st);
         if (status != ZK_OK) {
             (void)hipStreamSynchronize(st);
             return done(status);

@@ -1,7 +1,8 @@
 // Internals shared by the translation units of libzkcp_amd.so: the process context (one DeviceCtx per GPU the
 // process drives), per-stream scratch, the pool of MSM jobs (deferred results: enqueue -> event -> collect), and the
-// per-curve / per-field launch sequences that are explicitly instantiated in zk_msm_inst.cc / zk_ntt_inst.cc (one TU
-// per curve / field so the gfx950 code objects build in parallel).
+// per-curve / per-field launch sequences, the static members of CurveLaunch<C> / FieldLaunch<F> (zk_msm_decl.h /
+// zk_ntt_decl.h) that zk_msm_inst.cc / zk_ntt_inst.cc instantiate (one TU per curve / field so the gfx950 code objects
+// build in parallel).  The context and its helpers are defined in zk_runtime.cc.
 #pragma once
 #include "zkcp_amd.h"
 
@@ -59,7 +60,7 @@ struct BasesCopy {
 };
 constexpr int ZK_SHIFT_TABLES = 4;                 // 64-bit chunks of a scalar
 constexpr uint64_t ZK_SHIFT_AUTO_MIN = 1ull << 16; // smallest handle the collapse builds shift tables for by itself
-bool ipa_shift_tables_enabled();                   // ZK_IPA_SHIFT_TABLES=0 in the environment turns the table path off (zk_api.cc)
+bool ipa_shift_tables_enabled();                   // ZK_IPA_SHIFT_TABLES=0 in the environment turns the table path off (zk_runtime.cc)
 struct BasesEntry {
     int curve;
     uint64_t n;
@@ -236,7 +237,7 @@ inline int bind_device(DeviceCtx& dc) {
     HIP_TRY(hipSetDevice(dc.device));
     return ZK_OK;
 }
-int stream_scratch(DeviceCtx& dc, hipStream_t st, StreamScratch** out);   // zk_api.cc
+int stream_scratch(DeviceCtx& dc, hipStream_t st, StreamScratch** out);   // zk_runtime.cc
 
 int msm_pick_c(uint64_t n, int requested, bool pre = false);
 template <class C>

@@ -11,7 +11,7 @@ namespace zk {
 // IPA_S_SCRATCH_BYTES of tables where one proof allows it (k >= 22: fewer proofs a pass).
 constexpr size_t IPA_S_SCRATCH_BYTES = 64u << 20;
 template <class F>
-int ipa_s_run(DeviceCtx& dc, uint32_t k, uint32_t count, const void* u_host, const void* init_host, Fe<F>* s, int accumulate, hipStream_t st) {
+int FieldLaunch<F>::ipa_s_run(DeviceCtx& dc, uint32_t k, uint32_t count, const void* u_host, const void* init_host, Fe<F>* s, int accumulate, hipStream_t st) {
     if (k == 0 || k > (uint32_t)F::TWO_ADICITY || k > IPA_S_MAX_K || count == 0) return ZK_ERR_INVALID_ARG;
     const uint64_t n = 1ull << k;
     const uint32_t lb = k < IPA_S_LOW_BITS ? k : IPA_S_LOW_BITS;

@@ -7,8 +7,8 @@ namespace zk {
 // delta^col omega^row for mapping[c n + j] = col << 32 | row, n = 2^k.  *bad_mapping = 1 when a cell names a row >= n or a column
 // >= ncols (its slot holds 0; nothing was read through it).  Synchronises the stream once, at the end, to read the status word.
 template <class F>
-int perm_sigmas_run(DeviceCtx& dc, int field, uint32_t k, uint32_t ncols, const uint64_t* mapping, const Fe<F>& delta, const Fe<F>& omega,
-                    Fe<F>* sigmas, int* bad_mapping, hipStream_t st) {
+int FieldLaunch<F>::perm_sigmas_run(DeviceCtx& dc, int field, uint32_t k, uint32_t ncols, const uint64_t* mapping, const Fe<F>& delta, const Fe<F>& omega,
+                                    Fe<F>* sigmas, int* bad_mapping, hipStream_t st) {
     *bad_mapping = 0;
     if (ncols == 0 || k > 30 || k > (uint32_t)F::TWO_ADICITY) return ZK_ERR_INVALID_ARG;
     const uint64_t n = 1ull << k, cells = n * ncols;

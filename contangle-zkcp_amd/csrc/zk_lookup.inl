@@ -50,8 +50,8 @@ inline unsigned lk_key_blocks(const DeviceCtx& dc, uint64_t total) {
 }
 
 template <class F>
-int permute_expression_pair_run(DeviceCtx& dc, const Fe<F>* A, const Fe<F>* S, uint32_t u, Fe<F>* a_out, Fe<F>* s_out, int* lookup_failed,
-                                hipStream_t st) {
+int FieldLaunch<F>::permute_expression_pair_run(DeviceCtx& dc, const Fe<F>* A, const Fe<F>* S, uint32_t u, Fe<F>* a_out, Fe<F>* s_out, int* lookup_failed,
+                                                hipStream_t st) {
     static_assert(F::N == 8, "256-bit keys");
     static_assert(F::P[7] < 0x80000000u, "the modulus leaves bit 255 free for the input / table tag");
     *lookup_failed = 0;

@@ -7,8 +7,8 @@ namespace zk {
 // P programs at every row of the 2^k-row domain: status[p n + i], and vals[p n + i] when vals is given.  offs: n_programs + 1 op
 // offsets into prog (host).  Every program is validated on the host (expr_validate) before anything is launched.
 template <class F>
-int mock_eval_run(DeviceCtx& dc, uint32_t k, const zk_expr_op* prog, const uint32_t* offs, uint32_t n_programs, const void* const* cols,
-                  const uint64_t* poison_from, uint32_t n_cols, const Fe<F>* consts, uint32_t n_consts, Fe<F>* vals, uint8_t* status, hipStream_t st) {
+int FieldLaunch<F>::mock_eval_run(DeviceCtx& dc, uint32_t k, const zk_expr_op* prog, const uint32_t* offs, uint32_t n_programs, const void* const* cols,
+                                  const uint64_t* poison_from, uint32_t n_cols, const Fe<F>* consts, uint32_t n_consts, Fe<F>* vals, uint8_t* status, hipStream_t st) {
     if (k > 30 || k > (uint32_t)F::TWO_ADICITY || n_programs == 0 || n_programs > MOCK_MAX_PROGRAMS || offs[0] != 0) return ZK_ERR_INVALID_ARG;
     const uint64_t n = 1ull << k;
     for (uint32_t p = 0; p < n_programs; p++) {
@@ -47,8 +47,8 @@ int mock_eval_run(DeviceCtx& dc, uint32_t k, const zk_expr_op* prog, const uint3
 // positions / bytes of the first `cap` non-zero bytes of status[0 .. N), ascending, and their total.  The host arrays get
 // min(total, cap) entries; what lies past them is not touched.  Synchronises the stream once, at the end.
 template <class F>
-int mock_failures_run(DeviceCtx& dc, const uint8_t* status, uint64_t N, uint64_t cap, uint64_t* pos_host, uint8_t* kind_host, uint64_t* total_host,
-                      hipStream_t st) {
+int FieldLaunch<F>::mock_failures_run(DeviceCtx& dc, const uint8_t* status, uint64_t N, uint64_t cap, uint64_t* pos_host, uint8_t* kind_host, uint64_t* total_host,
+                                      hipStream_t st) {
     *total_host = 0;
     if (N == 0) return ZK_OK;
     if (cap > N) cap = N;
@@ -92,8 +92,8 @@ int mock_failures_run(DeviceCtx& dc, const uint8_t* status, uint64_t N, uint64_t
 // status[c n + r] of the copy constraints over the permutation's ncols columns; *bad_mapping = 1 when a mapping word names a
 // cell outside the grid (nothing was read through it).  Synchronises the stream once, at the end, to read the status word.
 template <class F>
-int mock_permutation_run(DeviceCtx& dc, uint32_t k, uint32_t ncols, const void* const* cols, const uint64_t* poison_from, const uint64_t* mapping,
-                         uint8_t* status, int* bad_mapping, hipStream_t st) {
+int FieldLaunch<F>::mock_permutation_run(DeviceCtx& dc, uint32_t k, uint32_t ncols, const void* const* cols, const uint64_t* poison_from, const uint64_t* mapping,
+                                         uint8_t* status, int* bad_mapping, hipStream_t st) {
     *bad_mapping = 0;
     if (ncols == 0 || k > 30 || k > (uint32_t)F::TWO_ADICITY) return ZK_ERR_INVALID_ARG;
     const uint64_t n = 1ull << k, cells = n * ncols;
@@ -128,8 +128,8 @@ int mock_permutation_run(DeviceCtx& dc, uint32_t k, uint32_t ncols, const void* 
 // status[r] = 1 iff input row r < u is not among table rows [0, u); a_status / s_status (optional): the evaluator's status bytes
 // of the two expressions, 2 = Poison.  Does not synchronise.
 template <class F>
-int mock_lookup_run(DeviceCtx& dc, const Fe<F>* A, const uint8_t* a_status, const Fe<F>* S, const uint8_t* s_status, uint32_t u, uint8_t* status,
-                    hipStream_t st) {
+int FieldLaunch<F>::mock_lookup_run(DeviceCtx& dc, const Fe<F>* A, const uint8_t* a_status, const Fe<F>* S, const uint8_t* s_status, uint32_t u, uint8_t* status,
+                                    hipStream_t st) {
     if (u == 0) return ZK_OK;
     StreamScratch* ss = nullptr;
     ZK_TRY(stream_scratch(dc, st, &ss));

@@ -1,4 +1,4 @@
-// MSM launch sequence and host tail.  Included by zk_msm_inst.cc, once per curve.
+// MSM launch sequence and host tail: members of CurveLaunch<C> (zk_msm_decl.h).  Included by zk_msm_inst.cc, once per curve.
 #pragma once
 #include "zk_internal.h"
 #include "zk_msm_decl.h"
@@ -374,7 +374,7 @@ constexpr bool has_f29() {
     return C::EXT == 1 || C::EXT == 2;
 }
 template <class C>
-int bases_prepare_run(BasesCopy& bc, uint64_t n) {
+int CurveLaunch<C>::bases_prepare_run(BasesCopy& bc, uint64_t n) {
     bc.dev29 = nullptr;
     if constexpr (has_f29<C>()) {
         if (n == 0) return ZK_OK;
@@ -415,7 +415,7 @@ int bases_multiples_run(BasesCopy& bc, uint64_t n, uint32_t bits, uint32_t rows,
 
 // the table of window multiples for the one-bucket-set form (zk_bases_precompute): nwin * n points
 template <class C>
-int bases_precompute_run(BasesCopy& bc, uint64_t n, int c) {
+int CurveLaunch<C>::bases_precompute_run(BasesCopy& bc, uint64_t n, int c) {
     const int nwin = msm_windows<C>(c);
     ZK_TRY(bases_multiples_run<C>(bc, n, (uint32_t)c, (uint32_t)nwin, &bc.pre));
     bc.pre_c = c;
@@ -425,12 +425,12 @@ int bases_precompute_run(BasesCopy& bc, uint64_t n, int c) {
 
 // the shift tables of the generator collapse (zk_bases_precompute_shifts): the same kernel with 64-bit "windows", [4][n] points
 template <class C>
-int bases_shifts_run(BasesCopy& bc, uint64_t n) {
+int CurveLaunch<C>::bases_shifts_run(BasesCopy& bc, uint64_t n) {
     return bases_multiples_run<C>(bc, n, 64u, (uint32_t)ZK_SHIFT_TABLES, &bc.shift);
 }
 
 template <class C>
-int bases_refresh_run(const BasesCopy& bc, uint64_t offset, uint64_t count, hipStream_t st) {
+int CurveLaunch<C>::bases_refresh_run(const BasesCopy& bc, uint64_t offset, uint64_t count, hipStream_t st) {
     if constexpr (has_f29<C>()) {
         if (!bc.dev29 || count == 0) return ZK_OK;
         ZK_LAUNCH((bases_to29_kernel<C>), (unsigned)((count + 255) / 256), 256, 0, st, (const Affine<C>*)bc.dev + offset,
@@ -442,7 +442,7 @@ int bases_refresh_run(const BasesCopy& bc, uint64_t offset, uint64_t count, hipS
 
 // every curve runs its bucket arithmetic in the lazy-limb view unless opts.limb_bits = 32 asks for the saturated words
 template <class C>
-int msm_enqueue(MsmJob& job, const BasesCopy& bc, const Fe<typename C::Fr>* d_scalars, uint64_t n, int mont, const MsmTuning& tu) {
+int CurveLaunch<C>::msm_enqueue(MsmJob& job, const BasesCopy& bc, const Fe<typename C::Fr>* d_scalars, uint64_t n, int mont, const MsmTuning& tu) {
     if constexpr (has_f29<C>()) {
         if (tu.precomputed) {
             if (!bc.pre || tu.base_offset != 0 || bc.pre_c != msm_pick_c(n, tu.window_bits, true) || bc.pre_w != msm_windows<C>(bc.pre_c))
@@ -456,7 +456,7 @@ int msm_enqueue(MsmJob& job, const BasesCopy& bc, const Fe<typename C::Fr>* d_sc
 }
 
 template <class C>
-uint32_t msm_batch_size(const BasesCopy& bc, uint64_t n, const MsmTuning& tu, int num_cus) {
+uint32_t CurveLaunch<C>::msm_batch_size(const BasesCopy& bc, uint64_t n, const MsmTuning& tu, int num_cus) {
     const int c = msm_pick_c(n, tu.window_bits, tu.precomputed), nwin = msm_windows<C>(c);
     const bool whole = tu.w0 == 0 && tu.w1 == 0;
     // (an empty window range makes an empty job whatever its batch: sized as one window)
@@ -468,15 +468,15 @@ uint32_t msm_batch_size(const BasesCopy& bc, uint64_t n, const MsmTuning& tu, in
 }
 
 template <class C>
-int fixed_base_run(const Fe<typename C::Fr>* d_scalars, uint64_t n, Affine<C>* d_out, hipStream_t st) {
+int CurveLaunch<C>::fixed_base_run(const Fe<typename C::Fr>* d_scalars, uint64_t n, Affine<C>* d_out, hipStream_t st) {
     ZK_LAUNCH((fixed_base_mul_kernel<C>), (unsigned)((n + 63) / 64), 64, 0, st, d_scalars, d_out, (uint32_t)n);
     HIP_TRY(hipGetLastError());
     return ZK_OK;
 }
 // ark-ec 0.3 FixedBaseMSM (window table + multi_scalar_mul) + batch_normalization_into_affine for one base
 template <class C>
-int fixed_base_msm_run(DeviceCtx& dc, const Affine<C>& base, const Fe<typename C::Fr>* d_scalars, uint64_t n, int mont, Affine<C>* d_out,
-                       hipStream_t st) {
+int CurveLaunch<C>::fixed_base_msm_run(DeviceCtx& dc, const Affine<C>& base, const Fe<typename C::Fr>* d_scalars, uint64_t n, int mont, Affine<C>* d_out,
+                                       hipStream_t st) {
     const uint32_t entries = (uint32_t)fb_windows<C>() * FB_ROW;
     StreamScratch* ss = nullptr;
     ZK_TRY(stream_scratch(dc, st, &ss));   // table and temporaries belong to the caller's stream
@@ -582,7 +582,7 @@ ZK_HD bool glv_decompose(const Fe<typename C::Fr>& u_canonical, FoldScalar& out)
 
 // g[i] <- affine(g[i] + [u] g[i + half]) for i < half (u canonical)
 template <class C>
-int ipa_fold_bases_run(DeviceCtx& dc, Affine<C>* gens, uint64_t half, const Fe<typename C::Fr>& u_canonical, hipStream_t st) {
+int CurveLaunch<C>::ipa_fold_bases_run(DeviceCtx& dc, Affine<C>* gens, uint64_t half, const Fe<typename C::Fr>& u_canonical, hipStream_t st) {
     if (half == 0) return ZK_OK;
     if (half >= (1ull << 31)) return ZK_ERR_UNSUPPORTED;
     StreamScratch* ss = nullptr;
@@ -611,8 +611,8 @@ int ipa_fold_bases_run(DeviceCtx& dc, Affine<C>* gens, uint64_t half, const Fe<t
 // have left in generators [first, first + count) (a rank's share of the survivors, or all of them) (zk_msm_kernels.h, "Several IPA rounds of generator folding at once").  w_dev: the weight vector of
 // the fold-free rounds; only W[t cur] is read (the weights do not depend on i).
 template <class C>
-int ipa_collapse_run(DeviceCtx& dc, const BasesCopy& bc, uint64_t base_n, const Fe<typename C::Fr>* w_dev, uint64_t m0, uint64_t cur,
-                     uint64_t first, uint64_t count, Affine<C>* g_out, hipStream_t st) {
+int CurveLaunch<C>::ipa_collapse_run(DeviceCtx& dc, const BasesCopy& bc, uint64_t base_n, const Fe<typename C::Fr>* w_dev, uint64_t m0, uint64_t cur,
+                                     uint64_t first, uint64_t count, Affine<C>* g_out, hipStream_t st) {
     using Fr = typename C::Fr;
     using CK = F29View<C>;
     if (cur == 0 || m0 == 0 || (m0 & (m0 - 1)) || (cur & (cur - 1)) || cur > m0 || m0 > base_n) return ZK_ERR_INVALID_ARG;

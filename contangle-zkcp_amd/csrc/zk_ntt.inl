@@ -1,4 +1,4 @@
-// NTT launch sequence (plan -> passes).  Included by zk_ntt_inst.cc, once per scalar field.
+// NTT launch sequence (plan -> passes): members of FieldLaunch<F> (zk_ntt_decl.h).  Included by zk_ntt_inst.cc, once per scalar field.
 #pragma once
 #include "zk_internal.h"
 #include "zk_ntt_decl.h"
@@ -155,13 +155,10 @@ int pow_tables(DeviceCtx& dc, const Fe<F>& gshift, uint32_t logn, int field, hip
     return ZK_OK;
 }
 
-template <class F>
-int vec_op_run(Fe<F>* a, const Fe<F>* b, const Fe<F>* c, uint64_t n, int op, const Fe<F>& s, hipStream_t st);
-
 // size-2^logn DFT of `a` with root omega; optionally fused with a[i] *= g_pre^i before and a[k] *= g_post^k after
 template <class F>
-int ntt_run(DeviceCtx& dc, int field, Fe<F>* a, uint32_t logn, const Fe<F>& omega, int scale_flag, hipStream_t st, const Fe<F>* g_pre,
-            const Fe<F>* g_post, uint32_t in_log, const Fe<F>* src0) {
+int FieldLaunch<F>::ntt_run(DeviceCtx& dc, int field, Fe<F>* a, uint32_t logn, const Fe<F>& omega, int scale_flag, hipStream_t st, const Fe<F>* g_pre,
+                            const Fe<F>* g_post, uint32_t in_log, const Fe<F>* src0) {
     // src0 (optional): the input is read from there by the first pass and left untouched; the result lands in `a` (out of place)
     if (!src0) src0 = a;
     if (logn > (uint32_t)F::TWO_ADICITY || logn > 30) return ZK_ERR_INVALID_ARG;   // before anything is sized from logn
@@ -172,7 +169,7 @@ int ntt_run(DeviceCtx& dc, int field, Fe<F>* a, uint32_t logn, const Fe<F>& omeg
             Fe<F> r;
             fe_one(r);
             for (int k = 0; k < F29<F>::W * F29<F>::L - 32 * F::N; k++) fe_dbl(r, r);
-            ZK_TRY(vec_op_run<F>(a, nullptr, nullptr, 1, VEC_SCALE, r, st));
+            ZK_TRY(vec_op_run(a, nullptr, nullptr, 1, VEC_SCALE, r, st));
         }
         return ZK_OK;
     }
@@ -287,7 +284,7 @@ int ntt_run(DeviceCtx& dc, int field, Fe<F>* a, uint32_t logn, const Fe<F>& omeg
 }
 
 template <class F>
-int coset_run(DeviceCtx& dc, int field, Fe<F>* a, uint32_t logn, const Fe<F>& gshift, hipStream_t st) {
+int FieldLaunch<F>::coset_run(DeviceCtx& dc, int field, Fe<F>* a, uint32_t logn, const Fe<F>& gshift, hipStream_t st) {
     if (logn > 30) return ZK_ERR_INVALID_ARG;
     const uint64_t count = 1ull << logn;
     PowTables<F> t;
@@ -300,7 +297,7 @@ int coset_run(DeviceCtx& dc, int field, Fe<F>* a, uint32_t logn, const Fe<F>& gs
 }
 
 template <class F>
-int vec_op_run(Fe<F>* a, const Fe<F>* b, const Fe<F>* c, uint64_t n, int op, const Fe<F>& s, hipStream_t st) {
+int FieldLaunch<F>::vec_op_run(Fe<F>* a, const Fe<F>* b, const Fe<F>* c, uint64_t n, int op, const Fe<F>& s, hipStream_t st) {
     if (n == 0) return ZK_OK;
     uint64_t blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;  // grid-stride: 16 workgroups per CU
@@ -310,7 +307,7 @@ int vec_op_run(Fe<F>* a, const Fe<F>* b, const Fe<F>* c, uint64_t n, int op, con
 }
 
 template <class F>
-int scale_periodic_run(Fe<F>* a, uint64_t n, const Fe<F>* table_host, uint32_t m, hipStream_t st) {
+int FieldLaunch<F>::scale_periodic_run(Fe<F>* a, uint64_t n, const Fe<F>* table_host, uint32_t m, hipStream_t st) {
     if (n == 0) return ZK_OK;
     if (m == 0 || m > 16 || (m & (m - 1)) != 0) return ZK_ERR_INVALID_ARG;
     PeriodicTable<F> t;
@@ -325,7 +322,7 @@ int scale_periodic_run(Fe<F>* a, uint64_t n, const Fe<F>* table_host, uint32_t m
 
 // out[0 .. n_rows) = M z, out[n_rows .. out_len) = 0   (CSR matrix resident on the device, see zk_r1cs_kernels.h)
 template <class F>
-int r1cs_matvec_run(const R1csMatrix& m, const Fe<F>* z, Fe<F>* out, uint64_t out_len, hipStream_t st) {
+int FieldLaunch<F>::r1cs_matvec_run(const R1csMatrix& m, const Fe<F>* z, Fe<F>* out, uint64_t out_len, hipStream_t st) {
     if (out_len < m.n_rows) return ZK_ERR_INVALID_ARG;
     if (out_len == 0) return ZK_OK;
     uint64_t blocks = (out_len + 255) / 256;
@@ -344,7 +341,7 @@ int r1cs_matvec_run(const R1csMatrix& m, const Fe<F>* z, Fe<F>* out, uint64_t ou
 //   ifft(a); ifft(b); coset_fft(a); coset_fft(b); ifft(c); coset_fft(c);
 //   ab = a.b - c;  ab *= 1/Z_H(g);  coset_ifft(ab)            -> `a` holds h (m coefficients, Montgomery)
 template <class F>
-int witness_map_run(DeviceCtx& dc, int field, Fe<F>* a, Fe<F>* b, Fe<F>* c, uint32_t logm, hipStream_t st) {
+int FieldLaunch<F>::witness_map_run(DeviceCtx& dc, int field, Fe<F>* a, Fe<F>* b, Fe<F>* c, uint32_t logm, hipStream_t st) {
     if (logm > (uint32_t)F::TWO_ADICITY || logm > 30) return ZK_ERR_INVALID_ARG;
     const uint64_t m = 1ull << logm;
     Fe<F> w, winv, gen, ginv, zinv, one;
@@ -363,11 +360,11 @@ int witness_map_run(DeviceCtx& dc, int field, Fe<F>* a, Fe<F>* b, Fe<F>* c, uint
     fe_inv(zinv, gm);
     Fe<F>* vs[3] = {a, b, c};
     for (int k = 0; k < 3; k++) {
-        ZK_TRY(ntt_run<F>(dc, field, vs[k], logm, winv, 1, st, nullptr, nullptr));   // ifft_in_place
-        ZK_TRY(ntt_run<F>(dc, field, vs[k], logm, w, 0, st, &gen, nullptr));          // coset_fft = distribute_powers(g) ; fft (fused)
+        ZK_TRY(ntt_run(dc, field, vs[k], logm, winv, 1, st, nullptr, nullptr));   // ifft_in_place
+        ZK_TRY(ntt_run(dc, field, vs[k], logm, w, 0, st, &gen, nullptr));          // coset_fft = distribute_powers(g) ; fft (fused)
     }
-    ZK_TRY(vec_op_run<F>(a, b, c, m, VEC_QAP, zinv, st));
-    ZK_TRY(ntt_run<F>(dc, field, a, logm, winv, 1, st, nullptr, &ginv));             // coset_ifft = ifft ; distribute_powers(g^-1) (fused)
+    ZK_TRY(vec_op_run(a, b, c, m, VEC_QAP, zinv, st));
+    ZK_TRY(ntt_run(dc, field, a, logm, winv, 1, st, nullptr, &ginv));             // coset_ifft = ifft ; distribute_powers(g^-1) (fused)
     return ZK_OK;
 }
 }  // namespace zk

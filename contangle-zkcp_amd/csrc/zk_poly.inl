@@ -7,7 +7,7 @@
 namespace zk {
 
 template <class F>
-int batch_invert_run(Fe<F>* a, uint64_t n, hipStream_t st) {
+int FieldLaunch<F>::batch_invert_run(Fe<F>* a, uint64_t n, hipStream_t st) {
     if (n == 0) return ZK_OK;
     const uint64_t lanes = (n + INV_K - 1) / INV_K;
     ZK_LAUNCH((batch_invert_kernel<F>), (unsigned)((lanes + 63) / 64), 64, 0, st, a, n);
@@ -17,7 +17,7 @@ int batch_invert_run(Fe<F>* a, uint64_t n, hipStream_t st) {
 
 // out[i] = first * prod_{j < i} in[j]  (in == out allowed); *total_dev (one element of scratch) = first * prod of all
 template <class F>
-int prefix_product_run(DeviceCtx& dc, const Fe<F>* in, Fe<F>* out, uint64_t n, const Fe<F>& first, Fe<F>** total_dev, hipStream_t st) {
+int FieldLaunch<F>::prefix_product_run(DeviceCtx& dc, const Fe<F>* in, Fe<F>* out, uint64_t n, const Fe<F>& first, Fe<F>** total_dev, hipStream_t st) {
     StreamScratch* ss = nullptr;
     ZK_TRY(stream_scratch(dc, st, &ss));
     const uint64_t per_wg = (uint64_t)SCAN_WG * SCAN_K;
@@ -37,12 +37,12 @@ int prefix_product_run(DeviceCtx& dc, const Fe<F>* in, Fe<F>* out, uint64_t n, c
 // f = num / den elementwise (den is inverted in place), then z = exclusive product scan of f
 template <class F>
 int ratio_scan_run(DeviceCtx& dc, Fe<F>* num, Fe<F>* den, uint64_t n, const Fe<F>& first, Fe<F>* z_out, void* total_host, hipStream_t st) {
-    ZK_TRY(batch_invert_run<F>(den, n, st));
+    ZK_TRY(FieldLaunch<F>::batch_invert_run(den, n, st));
     Fe<F> one;
     fe_one(one);
-    ZK_TRY(vec_op_run<F>(num, den, nullptr, n, VEC_MUL, one, st));
+    ZK_TRY(FieldLaunch<F>::vec_op_run(num, den, nullptr, n, VEC_MUL, one, st));
     Fe<F>* total = nullptr;
-    ZK_TRY(prefix_product_run<F>(dc, num, z_out, n, first, &total, st));
+    ZK_TRY(FieldLaunch<F>::prefix_product_run(dc, num, z_out, n, first, &total, st));
     if (total_host) {
         HIP_TRY(hipMemcpyAsync(total_host, total, sizeof(Fe<F>), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -51,9 +51,9 @@ int ratio_scan_run(DeviceCtx& dc, Fe<F>* num, Fe<F>* den, uint64_t n, const Fe<F
 }
 
 template <class F>
-int perm_product_run(DeviceCtx& dc, int field, uint32_t ncols, const void* const* cols, const void* const* sigmas, uint32_t first_col,
-                     const Fe<F>& beta, const Fe<F>& gamma, const Fe<F>& delta, uint32_t k, const Fe<F>& omega, const Fe<F>& first, Fe<F>* z_out,
-                     void* total_host, hipStream_t st) {
+int FieldLaunch<F>::perm_product_run(DeviceCtx& dc, int field, uint32_t ncols, const void* const* cols, const void* const* sigmas, uint32_t first_col,
+                                     const Fe<F>& beta, const Fe<F>& gamma, const Fe<F>& delta, uint32_t k, const Fe<F>& omega, const Fe<F>& first, Fe<F>* z_out,
+                                     void* total_host, hipStream_t st) {
     if (ncols == 0 || ncols > 8 || k > 30) return ZK_ERR_INVALID_ARG;
     const uint64_t n = 1ull << k;
     PermChunk<F> ch;
@@ -85,8 +85,8 @@ int perm_product_run(DeviceCtx& dc, int field, uint32_t ncols, const void* const
 }
 
 template <class F>
-int lookup_product_run(DeviceCtx& dc, const Fe<F>* A, const Fe<F>* S, const Fe<F>* Ap, const Fe<F>* Sp, const Fe<F>& beta, const Fe<F>& gamma,
-                       uint64_t n, const Fe<F>& first, Fe<F>* z_out, void* total_host, hipStream_t st) {
+int FieldLaunch<F>::lookup_product_run(DeviceCtx& dc, const Fe<F>* A, const Fe<F>* S, const Fe<F>* Ap, const Fe<F>* Sp, const Fe<F>& beta, const Fe<F>& gamma,
+                                       uint64_t n, const Fe<F>& first, Fe<F>* z_out, void* total_host, hipStream_t st) {
     StreamScratch* ss = nullptr;
     ZK_TRY(stream_scratch(dc, st, &ss));
     ZK_TRY(ws_get(ss->poly_a, (n ? n : 1) * sizeof(Fe<F>)));
@@ -100,7 +100,7 @@ int lookup_product_run(DeviceCtx& dc, const Fe<F>* A, const Fe<F>* S, const Fe<F
 
 // <a, b>: per-workgroup partial sums, added on the host (synchronises the stream)
 template <class F>
-int inner_product_run(DeviceCtx& dc, const Fe<F>* a, const Fe<F>* b, uint64_t n, void* out_host, hipStream_t st) {
+int FieldLaunch<F>::inner_product_run(DeviceCtx& dc, const Fe<F>* a, const Fe<F>* b, uint64_t n, void* out_host, hipStream_t st) {
     Fe<F> acc;
     fe_zero(acc);
     if (n) {
@@ -124,9 +124,9 @@ int inner_product_run(DeviceCtx& dc, const Fe<F>* a, const Fe<F>* b, uint64_t n,
 // and both inner products <p'_hi, b_lo>, <p'_lo, b_hi> are enqueued, their per-workgroup partial sums copied to pinned host
 // memory behind an event; ipa_round_end_run adds them up after the round's MSMs have been collected.
 template <class F>
-int ipa_round_begin_run(DeviceCtx& dc, const Fe<F>* p, const Fe<F>* b, const Fe<F>* W, Fe<F>* SL, Fe<F>* SR, uint64_t m0, uint64_t cur,
-                        hipStream_t st) {
-    ZK_TRY(ipa_virtual_scalars_run<F>(p, W, SL, SR, m0, cur, st));
+int FieldLaunch<F>::ipa_round_begin_run(DeviceCtx& dc, const Fe<F>* p, const Fe<F>* b, const Fe<F>* W, Fe<F>* SL, Fe<F>* SR, uint64_t m0, uint64_t cur,
+                                        hipStream_t st) {
+    ZK_TRY(ipa_virtual_scalars_run(p, W, SL, SR, m0, cur, st));
     const uint64_t half = cur / 2;
     StreamScratch* ss = nullptr;
     ZK_TRY(stream_scratch(dc, st, &ss));
@@ -155,7 +155,7 @@ int ipa_round_begin_run(DeviceCtx& dc, const Fe<F>* p, const Fe<F>* b, const Fe<
     return ZK_OK;
 }
 template <class F>
-int ipa_round_end_run(DeviceCtx& dc, hipStream_t st, void* vl_host, void* vr_host) {
+int FieldLaunch<F>::ipa_round_end_run(DeviceCtx& dc, hipStream_t st, void* vl_host, void* vr_host) {
     StreamScratch* ss = nullptr;
     ZK_TRY(stream_scratch(dc, st, &ss));
     if (!ss->pinned_ev) return ZK_ERR_INVALID_ARG;
@@ -189,7 +189,7 @@ int scratch_pow_tables(StreamScratch& ss, const Fe<F>& x, uint32_t logn, hipStre
 }
 
 template <class F>
-int vec_fold_many_run(Fe<F>* out, const Fe<F>* first, int64_t stride, uint32_t count, uint64_t n, const Fe<F>& s, hipStream_t st) {
+int FieldLaunch<F>::vec_fold_many_run(Fe<F>* out, const Fe<F>* first, int64_t stride, uint32_t count, uint64_t n, const Fe<F>& s, hipStream_t st) {
     if (n == 0 || count == 0) return ZK_OK;
     uint64_t blocks = (n + 255) / 256;
     if (blocks > 8192) blocks = 8192;
@@ -198,7 +198,7 @@ int vec_fold_many_run(Fe<F>* out, const Fe<F>* first, int64_t stride, uint32_t c
     return ZK_OK;
 }
 template <class F>
-int ipa_fold_round_run(Fe<F>* p, Fe<F>* b, Fe<F>* W, uint64_t half, uint64_t m0, const Fe<F>& u, hipStream_t st) {
+int FieldLaunch<F>::ipa_fold_round_run(Fe<F>* p, Fe<F>* b, Fe<F>* W, uint64_t half, uint64_t m0, const Fe<F>& u, hipStream_t st) {
     if (half == 0) return ZK_OK;
     if (W && (m0 == 0 || (m0 & (m0 - 1)) || half >= m0 || (half & (half - 1)))) return ZK_ERR_INVALID_ARG;
     Fe<F> ui;
@@ -211,7 +211,7 @@ int ipa_fold_round_run(Fe<F>* p, Fe<F>* b, Fe<F>* W, uint64_t half, uint64_t m0,
     return ZK_OK;
 }
 template <class F>
-int vec_powers_run(DeviceCtx& dc, Fe<F>* out, uint64_t n, const Fe<F>& x, hipStream_t st) {
+int FieldLaunch<F>::vec_powers_run(DeviceCtx& dc, Fe<F>* out, uint64_t n, const Fe<F>& x, hipStream_t st) {
     if (n == 0) return ZK_OK;
     if (n > (1ull << 30)) return ZK_ERR_UNSUPPORTED;
     uint32_t logn = 0;
@@ -229,7 +229,7 @@ int vec_powers_run(DeviceCtx& dc, Fe<F>* out, uint64_t n, const Fe<F>& x, hipStr
 
 // q = (a - a(x)) / (X - x), n coefficients in, n out (q[n - 1] = 0); a == q allowed  (zk_poly_kernels.h, kate_*)
 template <class F>
-int kate_division_run(DeviceCtx& dc, const Fe<F>* a, Fe<F>* q, uint64_t n, const Fe<F>& x, hipStream_t st) {
+int FieldLaunch<F>::kate_division_run(DeviceCtx& dc, const Fe<F>* a, Fe<F>* q, uint64_t n, const Fe<F>& x, hipStream_t st) {
     if (n == 0) return ZK_OK;
     if (n > (1ull << 30)) return ZK_ERR_UNSUPPORTED;
     StreamScratch* ss = nullptr;
@@ -259,8 +259,8 @@ int kate_division_run(DeviceCtx& dc, const Fe<F>* a, Fe<F>* q, uint64_t n, const
 // p_q(x) for `count` resident coefficient vectors of n elements (stride apart), all at the same x (Montgomery form): one
 // launch, one copy.  Synchronises the stream (the results are host values).
 template <class F>
-int poly_eval_run(DeviceCtx& dc, const Fe<F>* c, uint64_t n, uint32_t count, uint64_t stride, const Fe<F>& x, int field, void* out_host,
-                  hipStream_t st) {
+int FieldLaunch<F>::poly_eval_run(DeviceCtx& dc, const Fe<F>* c, uint64_t n, uint32_t count, uint64_t stride, const Fe<F>& x, int field, void* out_host,
+                                  hipStream_t st) {
     if (count == 0) return ZK_OK;
     std::vector<Fe<F>> acc(count);
     for (auto& a : acc) fe_zero(a);
@@ -295,7 +295,7 @@ int poly_eval_run(DeviceCtx& dc, const Fe<F>* c, uint64_t n, uint32_t count, uin
 }
 
 template <class F>
-int vec_muladd_run(Fe<F>* out, const Fe<F>* a, const Fe<F>* b, uint64_t n, const Fe<F>& s, hipStream_t st) {
+int FieldLaunch<F>::vec_muladd_run(Fe<F>* out, const Fe<F>* a, const Fe<F>* b, uint64_t n, const Fe<F>& s, hipStream_t st) {
     if (n == 0) return ZK_OK;
     uint64_t blocks = (n + 255) / 256;
     if (blocks > 8192) blocks = 8192;
@@ -305,7 +305,7 @@ int vec_muladd_run(Fe<F>* out, const Fe<F>* a, const Fe<F>* b, uint64_t n, const
 }
 
 template <class F>
-int vec_fold_run(Fe<F>* a, uint64_t half, const Fe<F>& c, hipStream_t st) {
+int FieldLaunch<F>::vec_fold_run(Fe<F>* a, uint64_t half, const Fe<F>& c, hipStream_t st) {
     if (half == 0) return ZK_OK;
     uint64_t blocks = (half + 255) / 256;
     if (blocks > 4096) blocks = 4096;
@@ -315,7 +315,7 @@ int vec_fold_run(Fe<F>* a, uint64_t half, const Fe<F>& c, hipStream_t st) {
 }
 
 template <class F>
-int ipa_virtual_scalars_run(const Fe<F>* p, const Fe<F>* W, Fe<F>* SL, Fe<F>* SR, uint64_t m0, uint64_t cur, hipStream_t st) {
+int FieldLaunch<F>::ipa_virtual_scalars_run(const Fe<F>* p, const Fe<F>* W, Fe<F>* SL, Fe<F>* SR, uint64_t m0, uint64_t cur, hipStream_t st) {
     if (m0 == 0 || cur < 2 || cur > m0 || (cur & (cur - 1)) != 0 || (m0 & (m0 - 1)) != 0) return ZK_ERR_INVALID_ARG;
     uint64_t blocks = (m0 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
@@ -324,7 +324,7 @@ int ipa_virtual_scalars_run(const Fe<F>* p, const Fe<F>* W, Fe<F>* SL, Fe<F>* SR
     return ZK_OK;
 }
 template <class F>
-int ipa_update_weights_run(Fe<F>* W, uint64_t m0, uint64_t bit, const Fe<F>& u, hipStream_t st) {
+int FieldLaunch<F>::ipa_update_weights_run(Fe<F>* W, uint64_t m0, uint64_t bit, const Fe<F>& u, hipStream_t st) {
     if (m0 == 0 || bit == 0 || bit >= m0 || (bit & (bit - 1)) != 0) return ZK_ERR_INVALID_ARG;
     uint64_t blocks = (m0 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
@@ -356,8 +356,8 @@ inline uint64_t expr_word(const zk_expr_op& o) { return (uint64_t)o.op | ((uint6
 
 // program / column table / constants are copied to the stream's scratch, then one grid-stride launch
 template <class F>
-int expr_eval_run(DeviceCtx& dc, const zk_expr_op* prog, uint32_t n_ops, const void* const* cols, uint32_t n_cols, const Fe<F>* consts,
-                  uint32_t n_consts, uint32_t log_n, uint32_t rot_scale, Fe<F>* out, hipStream_t st) {
+int FieldLaunch<F>::expr_eval_run(DeviceCtx& dc, const zk_expr_op* prog, uint32_t n_ops, const void* const* cols, uint32_t n_cols, const Fe<F>* consts,
+                                  uint32_t n_consts, uint32_t log_n, uint32_t rot_scale, Fe<F>* out, hipStream_t st) {
     if (log_n > 30) return ZK_ERR_INVALID_ARG;
     ZK_TRY(expr_validate(prog, n_ops, cols, n_cols, n_consts));
     StreamScratch* ss = nullptr;
@@ -719,7 +719,7 @@ inline int expr_jit_waves() {
 
 // the source of the specialised kernel for a program, without a device (zk_expr_specialised_source: diagnostics, the CPU test tier)
 template <class F>
-int expr_source_run(const zk_expr_op* prog, uint32_t n_ops, uint32_t n_cols, uint32_t n_consts, std::string& out) {
+int FieldLaunch<F>::expr_source_run(const zk_expr_op* prog, uint32_t n_ops, uint32_t n_cols, uint32_t n_consts, std::string& out) {
 #if !defined(ZK_EMU) && defined(ZK_FIELD)
     if (n_ops == 0 || n_ops > EXPR_MAX_OPS || n_cols > EXPR_MAX_COLS || n_consts > EXPR_MAX_CONSTS) return ZK_ERR_INVALID_ARG;
     std::vector<const void*> cols(n_cols ? n_cols : 1, (const void*)&out);      // (the walk only asks that a column be present)
@@ -737,8 +737,8 @@ int expr_source_run(const zk_expr_op* prog, uint32_t n_ops, uint32_t n_cols, uin
 
 // columns: x R' mod p (R' = 2^261), canonical words; constants: standard Montgomery on the host (converted here); out: standard
 template <class F>
-int expr_eval_lazy_run(DeviceCtx& dc, const zk_expr_op* prog, uint32_t n_ops, const void* const* cols, uint32_t n_cols, const Fe<F>* consts,
-                       uint32_t n_consts, uint32_t log_n, uint32_t rot_scale, Fe<F>* out, hipStream_t st) {
+int FieldLaunch<F>::expr_eval_lazy_run(DeviceCtx& dc, const zk_expr_op* prog, uint32_t n_ops, const void* const* cols, uint32_t n_cols, const Fe<F>* consts,
+                                       uint32_t n_consts, uint32_t log_n, uint32_t rot_scale, Fe<F>* out, hipStream_t st) {
     if (n_ops == 0 || n_ops > EXPR_MAX_OPS || n_cols > EXPR_MAX_COLS || n_consts > EXPR_MAX_CONSTS || log_n > 30) return ZK_ERR_INVALID_ARG;
     std::vector<uint64_t> words;
     uint32_t depth = 0;

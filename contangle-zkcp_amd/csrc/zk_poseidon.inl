@@ -1,5 +1,5 @@
 // Launch sequences of the Poseidon kernels (zk_poseidon_kernels.h) and their host twin.  Included by zk_ntt.inl, once per scalar
-// field.  Arguments are validated by the entry points (zk_api.cc); nothing here synchronises the stream.
+// field.  Arguments are validated by the entry points (zk_api_poseidon.cc); nothing here synchronises the stream.
 #pragma once
 #include "zk_host64.h"
 #include "zk_poseidon_kernels.h"
@@ -21,7 +21,7 @@ inline unsigned poseidon_grid(uint64_t count) {
 
 // ---- the host twin: the same permutation and sponge on 64-bit limbs (zk_host64.h), no device, no zk_init ----
 template <class F>
-int poseidon_permute_host_run(const PoseidonShape& sh, const Fe<F>* tbl, Fe<F>* states, uint64_t count) {
+int FieldLaunch<F>::poseidon_permute_host_run(const PoseidonShape& sh, const Fe<F>* tbl, Fe<F>* states, uint64_t count) {
     using K = H64<F>;
     static_assert(sizeof(Fe<K>) == sizeof(Fe<F>), "same bytes");
     POSEIDON_WIDTH_SWITCH(sh.width, {
@@ -35,7 +35,7 @@ int poseidon_permute_host_run(const PoseidonShape& sh, const Fe<F>* tbl, Fe<F>* 
     return ZK_OK;
 }
 template <class F>
-int poseidon_hash_host_run(const PoseidonShape& sh, const Fe<F>* tbl, const Fe<F>* in, uint32_t arity, uint64_t count, Fe<F>* out) {
+int FieldLaunch<F>::poseidon_hash_host_run(const PoseidonShape& sh, const Fe<F>* tbl, const Fe<F>* in, uint32_t arity, uint64_t count, Fe<F>* out) {
     using K = H64<F>;
     POSEIDON_WIDTH_SWITCH(sh.width, {
         for (uint64_t i = 0; i < count; i++) {
@@ -50,14 +50,14 @@ int poseidon_hash_host_run(const PoseidonShape& sh, const Fe<F>* tbl, const Fe<F
 
 // ---- device ----
 template <class F>
-int poseidon_permute_run(const PoseidonShape& sh, const Fe<F>* tbl, Fe<F>* states, uint64_t count, hipStream_t st) {
+int FieldLaunch<F>::poseidon_permute_run(const PoseidonShape& sh, const Fe<F>* tbl, Fe<F>* states, uint64_t count, hipStream_t st) {
     if (count == 0) return ZK_OK;
     POSEIDON_WIDTH_SWITCH(sh.width, ZK_LAUNCH((poseidon_permute_kernel<F, T>), poseidon_grid(count), POSEIDON_WG, 0, st, states, count, tbl, sh));
     HIP_TRY(hipGetLastError());
     return ZK_OK;
 }
 template <class F>
-int poseidon_hash_run(const PoseidonShape& sh, const Fe<F>* tbl, const Fe<F>* in, uint32_t arity, uint64_t count, Fe<F>* out, hipStream_t st) {
+int FieldLaunch<F>::poseidon_hash_run(const PoseidonShape& sh, const Fe<F>* tbl, const Fe<F>* in, uint32_t arity, uint64_t count, Fe<F>* out, hipStream_t st) {
     if (count == 0) return ZK_OK;
     POSEIDON_WIDTH_SWITCH(sh.width, ZK_LAUNCH((poseidon_hash_kernel<F, T>), poseidon_grid(count), POSEIDON_WG, 0, st, in, arity, count, out, tbl, sh));
     HIP_TRY(hipGetLastError());
@@ -66,11 +66,11 @@ int poseidon_hash_run(const PoseidonShape& sh, const Fe<F>* tbl, const Fe<F>* in
 // nodes[0 .. 2n - 1): the leaf digests, then every level behind the one below; 1 launch for the leaves, one per level of more than
 // 2^POSEIDON_TAIL_LOG nodes, one for all the levels above (a 2^20 tree: 1 + 11 + 1)
 template <class F>
-int poseidon_tree_run(const PoseidonShape& sh, const Fe<F>* tbl, const Fe<F>* leaves, uint32_t leaf_arity, uint32_t log_n, Fe<F>* nodes, hipStream_t st) {
+int FieldLaunch<F>::poseidon_tree_run(const PoseidonShape& sh, const Fe<F>* tbl, const Fe<F>* leaves, uint32_t leaf_arity, uint32_t log_n, Fe<F>* nodes, hipStream_t st) {
     uint64_t m = 1ull << log_n, off = 0;
-    ZK_TRY(poseidon_hash_run<F>(sh, tbl, leaves, leaf_arity, m, nodes, st));
+    ZK_TRY(poseidon_hash_run(sh, tbl, leaves, leaf_arity, m, nodes, st));
     while (m > 2 * POSEIDON_WG) {
-        ZK_TRY(poseidon_hash_run<F>(sh, tbl, nodes + off, 2, m / 2, nodes + off + m, st));
+        ZK_TRY(poseidon_hash_run(sh, tbl, nodes + off, 2, m / 2, nodes + off + m, st));
         off += m;
         m /= 2;
     }
@@ -80,7 +80,7 @@ int poseidon_tree_run(const PoseidonShape& sh, const Fe<F>* tbl, const Fe<F>* le
 }
 // idx: host, every entry < 2^log_n (checked by the caller); out: count x log_n siblings, bottom-up
 template <class F>
-int merkle_paths_run(const Fe<F>* nodes, uint32_t log_n, const uint64_t* idx, uint64_t count, Fe<F>* out, hipStream_t st) {
+int FieldLaunch<F>::merkle_paths_run(const Fe<F>* nodes, uint32_t log_n, const uint64_t* idx, uint64_t count, Fe<F>* out, hipStream_t st) {
     for (uint64_t c0 = 0; c0 < count; c0 += MERKLE_PATHS_PER_LAUNCH) {
         const uint32_t c = (uint32_t)(count - c0 < MERKLE_PATHS_PER_LAUNCH ? count - c0 : MERKLE_PATHS_PER_LAUNCH);
         MerklePathIndices ix;
@@ -91,7 +91,7 @@ int merkle_paths_run(const Fe<F>* nodes, uint32_t log_n, const uint64_t* idx, ui
     return ZK_OK;
 }
 template <class F>
-int vec_add_scalar_run(Fe<F>* out, const Fe<F>* a, uint64_t n, const Fe<F>& s, hipStream_t st) {
+int FieldLaunch<F>::vec_add_scalar_run(Fe<F>* out, const Fe<F>* a, uint64_t n, const Fe<F>& s, hipStream_t st) {
     if (n == 0) return ZK_OK;
     uint64_t blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;

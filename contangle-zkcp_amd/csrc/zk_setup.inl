@@ -6,7 +6,7 @@ namespace zk {
 // The column-major companion of a resident CSR matrix, on the device: histogram of col_idx, exclusive scan, scatter.  Runs once
 // per handle (the caller holds the matrix table's lock) and synchronises `st` at the end to read the number of long columns.
 template <class F>
-int r1cs_transpose_run(R1csMatrix& m, hipStream_t st) {
+int FieldLaunch<F>::r1cs_transpose_run(R1csMatrix& m, hipStream_t st) {
     if (m.t_ready) return ZK_OK;
     if (m.nnz >= (1ull << 32) || m.n_rows >= (1ull << 32)) return ZK_ERR_UNSUPPORTED;   // 32-bit offsets and row indices
     const uint64_t n_ptr = m.n_cols + 1;
@@ -57,8 +57,8 @@ int r1cs_transpose_run(R1csMatrix& m, hipStream_t st) {
 
 // out[j] = sum_{i < x_len} M[i][j] x[i] (+ extra[j], j < n_extra) for j < n_cols; extra[j] or 0 for n_cols <= j < out_len
 template <class F>
-int r1cs_matvec_t_run(const R1csMatrix& m, const Fe<F>* x, uint64_t x_len, Fe<F>* out, uint64_t out_len, const Fe<F>* extra, uint64_t n_extra,
-                      hipStream_t st) {
+int FieldLaunch<F>::r1cs_matvec_t_run(const R1csMatrix& m, const Fe<F>* x, uint64_t x_len, Fe<F>* out, uint64_t out_len, const Fe<F>* extra, uint64_t n_extra,
+                                      hipStream_t st) {
     if (!m.t_ready || out_len < m.n_cols || n_extra > out_len) return ZK_ERR_INVALID_ARG;
     if (out_len == 0) return ZK_OK;
     uint64_t blocks = (out_len + 255) / 256;
@@ -75,7 +75,7 @@ int r1cs_matvec_t_run(const R1csMatrix& m, const Fe<F>* x, uint64_t x_len, Fe<F>
 // the host constants of the size-2^logm domain at tau: w = its generator, zt = tau^m - 1 (ZK_ERR_INVALID_ARG when tau lies in
 // the domain: upstream samples tau outside it and has no use for that branch), s = zt / m
 template <class F>
-int lagrange_consts(uint32_t logm, const Fe<F>& tau, Fe<F>* w_out, Fe<F>* zt_out, Fe<F>* s_out) {
+int FieldLaunch<F>::lagrange_consts(uint32_t logm, const Fe<F>& tau, Fe<F>* w_out, Fe<F>* zt_out, Fe<F>* s_out) {
     if (logm > (uint32_t)F::TWO_ADICITY || logm > 30) return ZK_ERR_INVALID_ARG;
     Fe<F> w, tm = tau, one, mm, minv;
     for (int i = 0; i < F::N; i++) w.v[i] = F::ROOT[i];
@@ -97,16 +97,16 @@ int lagrange_consts(uint32_t logm, const Fe<F>& tau, Fe<F>* w_out, Fe<F>* zt_out
 
 // ark-poly 0.3 Radix2EvaluationDomain::evaluate_all_lagrange_coefficients(tau), tau outside the domain: out[i] = L_i(tau), i < 2^logm
 template <class F>
-int lagrange_run(DeviceCtx& dc, int field, uint32_t logm, const Fe<F>& tau, Fe<F>* out, Fe<F>* zt_out, hipStream_t st) {
+int FieldLaunch<F>::lagrange_run(DeviceCtx& dc, int field, uint32_t logm, const Fe<F>& tau, Fe<F>* out, Fe<F>* zt_out, hipStream_t st) {
     Fe<F> w, zt, s;
-    ZK_TRY(lagrange_consts<F>(logm, tau, &w, &zt, &s));
+    ZK_TRY(lagrange_consts(logm, tau, &w, &zt, &s));
     const uint64_t m = 1ull << logm;
     PowTables<F> pw;
     ZK_TRY(pow_tables<F>(dc, w, logm, field, st, &pw));
     uint64_t blocks = (m + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     ZK_LAUNCH((lagrange_den_kernel<F>), (unsigned)blocks, 256, 0, st, out, m, tau, pw);
-    ZK_TRY(batch_invert_run<F>(out, m, st));
+    ZK_TRY(batch_invert_run(out, m, st));
     ZK_LAUNCH((lagrange_scale_kernel<F>), (unsigned)blocks, 256, 0, st, out, m, s, pw);
     HIP_TRY(hipGetLastError());
     if (zt_out) *zt_out = zt;
@@ -116,26 +116,26 @@ int lagrange_run(DeviceCtx& dc, int field, uint32_t logm, const Fe<F>& tau, Fe<F
 // r1cs_to_qap.rs LibsnarkReduction::instance_map_with_evaluation: u, v, w (n_vars elements each) from the three resident
 // matrices (their column-major companions ready) at tau; the Lagrange vector lives in the stream's scratch
 template <class F>
-int groth16_qap_at_run(DeviceCtx& dc, int field, const R1csMatrix& ma, const R1csMatrix& mb, const R1csMatrix& mc, uint64_t num_inputs,
-                       uint32_t logm, const Fe<F>& tau, Fe<F>* u, Fe<F>* v, Fe<F>* w, uint64_t n_vars, Fe<F>* zt_out, hipStream_t st) {
+int FieldLaunch<F>::groth16_qap_at_run(DeviceCtx& dc, int field, const R1csMatrix& ma, const R1csMatrix& mb, const R1csMatrix& mc, uint64_t num_inputs,
+                                       uint32_t logm, const Fe<F>& tau, Fe<F>* u, Fe<F>* v, Fe<F>* w, uint64_t n_vars, Fe<F>* zt_out, hipStream_t st) {
     const uint64_t m = 1ull << logm, nc = ma.n_rows;
     StreamScratch* ss = nullptr;
     ZK_TRY(stream_scratch(dc, st, &ss));
     ZK_TRY(ws_get(ss->poly_a, m * sizeof(Fe<F>)));
     Fe<F>* L = (Fe<F>*)ss->poly_a.p;
-    ZK_TRY(lagrange_run<F>(dc, field, logm, tau, L, zt_out, st));
+    ZK_TRY(lagrange_run(dc, field, logm, tau, L, zt_out, st));
     // u_j = sum_i A[i][j] L_i + L_{num_constraints + j} for the inputs: the input-consistency rows, added by the same pass
-    ZK_TRY(r1cs_matvec_t_run<F>(ma, L, m, u, n_vars, L + nc, num_inputs, st));
-    ZK_TRY(r1cs_matvec_t_run<F>(mb, L, m, v, n_vars, nullptr, 0, st));
-    ZK_TRY(r1cs_matvec_t_run<F>(mc, L, m, w, n_vars, nullptr, 0, st));
+    ZK_TRY(r1cs_matvec_t_run(ma, L, m, u, n_vars, L + nc, num_inputs, st));
+    ZK_TRY(r1cs_matvec_t_run(mb, L, m, v, n_vars, nullptr, 0, st));
+    ZK_TRY(r1cs_matvec_t_run(mc, L, m, w, n_vars, nullptr, 0, st));
     return ZK_OK;
 }
 
 // generator.rs generate_parameters, the scalars of gamma_abc_g1 | l_query (abc, n_vars elements) and of h_query (h, 2^logm - 1)
 template <class F>
-int groth16_key_scalars_run(DeviceCtx& dc, const Fe<F>* u, const Fe<F>* v, const Fe<F>* w, uint64_t n_vars, uint64_t num_inputs, uint32_t logm,
-                            const Fe<F>& alpha, const Fe<F>& beta, const Fe<F>& gamma, const Fe<F>& delta, const Fe<F>& tau, const Fe<F>& zt,
-                            Fe<F>* abc, Fe<F>* h, hipStream_t st) {
+int FieldLaunch<F>::groth16_key_scalars_run(DeviceCtx& dc, const Fe<F>* u, const Fe<F>* v, const Fe<F>* w, uint64_t n_vars, uint64_t num_inputs, uint32_t logm,
+                                            const Fe<F>& alpha, const Fe<F>& beta, const Fe<F>& gamma, const Fe<F>& delta, const Fe<F>& tau, const Fe<F>& zt,
+                                            Fe<F>* abc, Fe<F>* h, hipStream_t st) {
     if (logm > 30 || fe_is_zero(gamma) || fe_is_zero(delta) || fe_is_zero(zt)) return ZK_ERR_INVALID_ARG;
     Fe<F> ginv, dinv, s;
     fe_inv(ginv, gamma);
