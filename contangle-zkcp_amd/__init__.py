@@ -531,6 +531,6 @@ def fixed_base_msm_device(curve, d_scalars, d_out, n, base=None, montgomery=Fals
                                            _ptr(d_out), ctypes.c_void_p(stream)), "zk_fixed_base_msm_device")
 
 
-from . import ark, ark_serialize, groth16, halo2, poseidon  # noqa: E402,F401  (interface mirrors)
+from . import ark, ark_serialize, groth16, halo2, poseidon, jubjub, r1cs, encryption  # noqa: E402,F401  (interface mirrors)
 
-PROVER_EXPORTS = groth16.PROVER_EXPORTS + halo2.PROVER_EXPORTS + poseidon.PROVER_EXPORTS
+PROVER_EXPORTS = groth16.PROVER_EXPORTS + halo2.PROVER_EXPORTS + poseidon.PROVER_EXPORTS + encryption.PROVER_EXPORTS

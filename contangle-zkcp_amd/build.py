@@ -19,7 +19,7 @@ CURVES = ["Pallas", "Vesta", "Bn254G1", "Bls381G1", "Bn254G2", "Bls381G2"]
 FIELDS = ["PallasFp", "PallasFq", "Bn254Fr", "Bls381Fr"]
 # (source, extra define, object tag)
 UNITS = [("zk_runtime.cc", None, "runtime")] + \
-        [("zk_api_%s.cc" % s, None, "api_" + s) for s in ("bases", "msm", "field", "groth16", "halo2", "poseidon")] + \
+        [("zk_api_%s.cc" % s, None, "api_" + s) for s in ("bases", "msm", "field", "groth16", "halo2", "poseidon", "encrypt")] + \
         [("zk_wire.cc", None, "wire"), ("zk_pairing.cc", None, "pairing")] + \
         [("zk_msm_inst.cc", "ZK_CURVE=" + c, "msm_" + c) for c in CURVES] + \
         [("zk_ntt_inst.cc", "ZK_FIELD=" + f, "ntt_" + f) for f in FIELDS]

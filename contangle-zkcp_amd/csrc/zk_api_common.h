@@ -32,6 +32,17 @@ inline bool spans_overlap(const void* a, uint64_t a_bytes, const void* b, uint64
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return x < y + b_bytes && y < x + a_bytes;
 }
+// `count` host elements of F::N words each, every one below the modulus
+template <class F>
+bool canonical_elems(const void* p, size_t count) {
+    const uint32_t* w = (const uint32_t*)p;
+    for (size_t e = 0; e < count; e++, w += F::N) {
+        int i = F::N - 1;
+        while (i >= 0 && w[i] == F::P[i]) i--;
+        if (i < 0 || w[i] > F::P[i]) return false;
+    }
+    return true;
+}
 template <class C>
 void jac_to_xyzz(XYZZ<C>& r, const Jacobian<C>& j) {
     if (fe_is_zero(j.z)) {

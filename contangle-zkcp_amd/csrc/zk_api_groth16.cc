@@ -121,6 +121,24 @@ API int zk_groth16_witness_map_r1cs_device(zk_field_t f, uint64_t ha, uint64_t h
     return ZK_ERR_INVALID_ARG;
 }
 
+// ark-relations ConstraintSystem::is_satisfied, naming the row: the smallest i with <A_i, z> <B_i, z> != <C_i, z>
+API int zk_r1cs_first_unsatisfied_device(zk_field_t f, uint64_t ha, uint64_t hb, uint64_t hc, const void* z, uint64_t z_len, void* scratch,
+                                         uint64_t scratch_elems, uint64_t* first_row_out_host, void* stream) {
+    if (!z || !scratch || !first_row_out_host || !aligned16(z) || !aligned16(scratch)) return ZK_ERR_INVALID_ARG;
+    R1csMatrix ma, mb, mc;
+    ZK_TRY(find_matrix(ha, &ma));
+    ZK_TRY(find_matrix(hb, &mb));
+    ZK_TRY(find_matrix(hc, &mc));
+    const uint64_t rows = ma.n_rows;
+    if (ma.field != (int)f || mb.field != (int)f || mc.field != (int)f || mb.n_rows != rows || mc.n_rows != rows || z_len < ma.n_cols ||
+        z_len < mb.n_cols || z_len < mc.n_cols || scratch_elems < 3 * rows + ZK_R1CS_CHECK_SCRATCH_ELEMS ||
+        spans_overlap(z, z_len * 32, scratch, scratch_elems * 32))
+        return ZK_ERR_INVALID_ARG;
+    DEVICE_ENTRY(nullptr);
+    FIELD_SWITCH(f, return FieldLaunch<F>::r1cs_first_unsatisfied_run(ma, mb, mc, (const Fe<F>*)z, (Fe<F>*)scratch, first_row_out_host, (hipStream_t)stream));
+    return ZK_ERR_INVALID_ARG;
+}
+
 // ---- Groth16 key generation (ark-groth16 0.3 generator.rs generate_parameters)
 // the matrix with its column-major companion, which is built on `st` at the handle's first transposed product
 static int find_matrix_transposed(uint64_t handle, hipStream_t st, R1csMatrix* out) {

@@ -29,16 +29,6 @@ void free_poseidon_tables(PoseidonEntry& e) {   // (g.mu and g_pos_mu held)
     e.dev.clear();
 }
 
-template <class F>
-bool canonical_elems(const void* p, size_t count) {
-    const uint32_t* w = (const uint32_t*)p;
-    for (size_t e = 0; e < count; e++, w += F::N) {
-        int i = F::N - 1;
-        while (i >= 0 && w[i] == F::P[i]) i--;
-        if (i < 0 || w[i] > F::P[i]) return false;
-    }
-    return true;
-}
 int find_poseidon(uint64_t handle, std::shared_ptr<PoseidonEntry>* out) {
     std::lock_guard<std::mutex> lk(g_pos_mu);
     auto it = g_poseidon.find(handle);

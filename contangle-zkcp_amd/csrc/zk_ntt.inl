@@ -375,3 +375,4 @@ int FieldLaunch<F>::witness_map_run(DeviceCtx& dc, int field, Fe<F>* a, Fe<F>* b
 #include "zk_ipa_verify.inl"
 #include "zk_mock.inl"
 #include "zk_poseidon.inl"
+#include "zk_encrypt.inl"

@@ -93,5 +93,10 @@ struct FieldLaunch {
     static int poseidon_tree_run(const PoseidonShape& sh, const Fe<F>* tbl, const Fe<F>* leaves, uint32_t leaf_arity, uint32_t log_n, Fe<F>* nodes, hipStream_t st);
     static int merkle_paths_run(const Fe<F>* nodes, uint32_t log_n, const uint64_t* idx_host, uint64_t count, Fe<F>* out, hipStream_t st);
     static int vec_add_scalar_run(Fe<F>* out, const Fe<F>* a, uint64_t n, const Fe<F>& s, hipStream_t st);
+    // EncryptCircuit: the per-element witness, the plaintext of a byte string, the first unsatisfied row (zk_encrypt.inl)
+    static int encrypt_witness_run(const Fe<F>* msg, uint64_t msg_len, uint64_t n, const Fe<F>& dh, Fe<F>* c2, Fe<F>* m, Fe<F>* b, Fe<F>* k, hipStream_t st);
+    static int plaintext_from_bytes_run(const uint8_t* bytes, uint64_t len, Fe<F>* out, uint64_t n, hipStream_t st);
+    static int r1cs_first_unsatisfied_run(const R1csMatrix& ma, const R1csMatrix& mb, const R1csMatrix& mc, const Fe<F>* z, Fe<F>* scratch,
+                                          uint64_t* first_row_out, hipStream_t st);
 };
 }  // namespace zk

@@ -29,7 +29,7 @@ from . import (Bases, _check, _np64, _ptr, ark_serialize, backend_info, base_lim
 PROVER_EXPORTS = ["zk_r1cs_matrix_upload", "zk_r1cs_matrix_free", "zk_r1cs_matvec_device", "zk_groth16_witness_map_r1cs_device",
                   "zk_groth16_assemble_proof", "zk_r1cs_matvec_transposed_device", "zk_lagrange_coefficients_device",
                   "zk_groth16_qap_at_device", "zk_groth16_key_scalars_device", "zk_pairing_product", "zk_groth16_verify",
-                  "zk_groth16_prepare_inputs"]
+                  "zk_groth16_prepare_inputs", "zk_r1cs_first_unsatisfied_device"]
 
 
 class Assembly(ctypes.Structure):
@@ -56,6 +56,7 @@ def _lib():
     lib.zk_pairing_product.argtypes = [i32, vp, vp, u64, vp]
     lib.zk_groth16_verify.argtypes = [i32, ctypes.POINTER(VkPoints), vp, vp, vp, vp, vp, ctypes.POINTER(u64)]
     lib.zk_groth16_prepare_inputs.argtypes = [i32, u64, vp, u64, vp, u64, vp, vp]
+    lib.zk_r1cs_first_unsatisfied_device.argtypes = [i32, u64, u64, u64, vp, u64, vp, u64, ctypes.POINTER(u64), vp]
     return lib
 
 
@@ -117,6 +118,20 @@ def witness_map(field, A, B, C, d_z, num_inputs, d_a, d_b, d_c, stream=0):
     return d_a
 
 
+R1CS_CHECK_SCRATCH_ELEMS = 256   # ZK_R1CS_CHECK_SCRATCH_ELEMS
+
+
+def first_unsatisfied(A, B, C, d_z, stream=0):
+    """ConstraintSystem::is_satisfied on the device, naming the row: the smallest i with <A_i, z> <B_i, z> != <C_i, z>, None when the
+    assignment d_z (device buffer, canonical Montgomery) satisfies every row.  Synchronises the stream."""
+    d_scratch = _new_buffer((3 * A.n_rows + R1CS_CHECK_SCRATCH_ELEMS, 4))
+    row = ctypes.c_uint64(0)
+    _check(_lib().zk_r1cs_first_unsatisfied_device(A.field, A.handle, B.handle, C.handle, _ptr(d_z), int(d_z.shape[0]), _ptr(d_scratch),
+                                                   int(d_scratch.shape[0]), ctypes.byref(row), ctypes.c_void_p(stream)),
+           "zk_r1cs_first_unsatisfied_device")
+    return None if row.value == (1 << 64) - 1 else row.value
+
+
 def assemble_proof(pairing, key_points, accs, r, s):
     """key_points: alpha_g1, beta_g1, delta_g1, beta_g2, delta_g2, a_query0, b_g1_query0, b_g2_query0 (affine Montgomery limbs);
     accs: a_acc, b_g1_acc, l_acc, h_acc, b_g2_acc (Jacobian MSM results); r, s: Fr Montgomery limbs -> (A, B, C) affine"""
@@ -152,12 +167,15 @@ class Prover:
 
     def prove(self, z_mont, r_mont, s_mont, stream=0):
         """z_mont: full assignment [num_vars, 4] Montgomery limbs, z[0] = 1 -> (A, B, C) affine points and the proof bytes"""
-        z_mont = _np64(z_mont)
+        return self.prove_device(self.to_device(_np64(z_mont)), r_mont, s_mont, stream=stream)
+
+    def prove_device(self, d_z, r_mont, s_mont, stream=0):
+        """`prove` from a resident assignment (e.g. encryption.EncryptCircuit.assign): no upload, and one device copy of d_z for the
+        canonical form the MSMs read; d_z itself is left as it is"""
         ni, m = self.num_inputs, self.m
-        d_z = self.to_device(z_mont)
-        d_abc = [self.to_device(np.zeros((m, 4), dtype=np.uint64)) for _ in range(3)]
+        d_abc = [_new_buffer((m, 4)) for _ in range(3)]                  # made on the device: the mat-vecs write all m entries
         d_h = witness_map(self.field, self.A, self.B, self.C, d_z, ni, d_abc[0], d_abc[1], d_abc[2], stream=stream)
-        d_zc = self.to_device(z_mont)
+        d_zc = d_z.copy() if isinstance(d_z, np.ndarray) else d_z.clone()
         vec_op(self.field, "into_repr", d_zc, stream=stream)             # the MSMs over z take canonical BigInts, like upstream
         # at most four MSMs in flight per device: submit four, collect one, submit the fifth.  The G2 MSM goes first: its host
         # tail (the Horner over the windows on Fq2 host limbs) is the longest of the five and then runs beside the G1 MSMs' device work

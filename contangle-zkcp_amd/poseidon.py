@@ -80,6 +80,9 @@ class PoseidonParameters:
                "zk_poseidon_create")
         self.handle = h.value
         self.init = [int(x) % self.p for x in init] if init is not None else [0] * self.width
+        # the constants as integers: the R1CS gadget (r1cs.poseidon_permute) writes them into its rows
+        self.ark = [[int(x) % self.p for x in row] for row in ark]
+        self.mds = [[int(x) % self.p for x in row] for row in mds]
 
     def permute(self, state):
         """one permutation of `width` integers on the host twin"""

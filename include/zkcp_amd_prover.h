@@ -485,6 +485,31 @@ int zk_merkle_paths_device(zk_field_t f, const void *nodes_dev, uint32_t log_n, 
 /* out[i] = a[i] + s, i < n (encrypt: s = dh; decrypt: s = -dh).  out_dev may be a_dev itself; any other overlap is refused. */
 int zk_vec_add_scalar_device(zk_field_t f, void *out_dev, const void *a_dev, uint64_t n, const void *scalar_mont_host, void *hip_stream);
 
+/* ---- EncryptCircuit (circuits-ark/src/encryption.rs; DESIGN.md section 5, "EncryptCircuit") ----
+ * The per-element section of the circuit's assignment, in one launch.  For i < n, with dh the Poseidon digest of the shared point:
+ *   m[i]  = msg[i] for i < msg_len, else 0
+ *   c2[i] = m[i] + dh for i < msg_len, else 0
+ *   b[i]  = 1 if c2[i] != 0, else 0               ("the ciphertext element is not empty")
+ *   k[i]  = 1 / c2[i], or 1 where c2[i] = 0       (the multiplier of upstream's is_neq gadget)
+ * Elements are 4 u64 words, Montgomery, canonical.  One field inversion per lane is shared among the 16 elements the lane owns.  The four
+ * outputs are n elements each, independent of one another: in practice four segments of the assignment.  msg_dev may be NULL when
+ * msg_len = 0.  Does not synchronise.
+ * ZK_ERR_INVALID_ARG, before anything is launched: a null or not 16-B aligned pointer; two outputs, or an output and msg, that share
+ * an address; msg_len > n; n > 2^40; dh >= p. */
+int zk_encrypt_witness_device(zk_field_t f, const void *msg_dev, uint64_t msg_len, uint64_t n, const void *dh_mont_host, void *c2_dev, void *m_dev,
+                              void *b_dev, void *k_dev, void *hip_stream);
+/* bytes_to_plaintext_chunks_direct (utils.rs:60-72): out[i] = byte i as a field element (Montgomery) for i < len, 0 for len <= i < n.
+ * Bytes from n on are not read.  Does not synchronise. */
+int zk_plaintext_from_bytes_device(zk_field_t f, const uint8_t *bytes_dev, uint64_t len, void *out_dev, uint64_t n, void *hip_stream);
+/* ConstraintSystem::is_satisfied, naming the row: *first_row_out_host = the smallest i with <A_i, z> <B_i, z> != <C_i, z>, UINT64_MAX
+ * when every row holds.  a, b, c: handles of zk_r1cs_matrix_upload with equal row counts; z_dev: z_len >= their column counts
+ * canonical Montgomery elements; scratch_dev: scratch_elems >= 3 rows + ZK_R1CS_CHECK_SCRATCH_ELEMS elements, 16-B aligned, apart
+ * from z.  Three mat-vecs and one compare kernel that reduces by minimum in a fixed order (the same row on every run); synchronises
+ * hip_stream once, at the end. */
+#define ZK_R1CS_CHECK_SCRATCH_ELEMS 256
+int zk_r1cs_first_unsatisfied_device(zk_field_t f, uint64_t a, uint64_t b, uint64_t c, const void *z_dev, uint64_t z_len, void *scratch_dev,
+                                     uint64_t scratch_elems, uint64_t *first_row_out_host, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

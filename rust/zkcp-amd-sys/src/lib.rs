@@ -297,6 +297,11 @@ extern "C" {
                                   hip_stream: *mut c_void) -> c_int;
     pub fn zk_vec_add_scalar_device(f: c_int, out_dev: *mut c_void, a_dev: *const c_void, n: u64, scalar_mont_host: *const c_void,
                                     hip_stream: *mut c_void) -> c_int;
+    pub fn zk_encrypt_witness_device(f: c_int, msg_dev: *const c_void, msg_len: u64, n: u64, dh_mont_host: *const c_void, c2_dev: *mut c_void,
+                                     m_dev: *mut c_void, b_dev: *mut c_void, k_dev: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn zk_plaintext_from_bytes_device(f: c_int, bytes_dev: *const u8, len: u64, out_dev: *mut c_void, n: u64, hip_stream: *mut c_void) -> c_int;
+    pub fn zk_r1cs_first_unsatisfied_device(f: c_int, a: u64, b: u64, c: u64, z_dev: *const c_void, z_len: u64, scratch_dev: *mut c_void,
+                                            scratch_elems: u64, first_row_out_host: *mut u64, hip_stream: *mut c_void) -> c_int;
     pub fn zk_inner_product_device(f: c_int, a_dev: *const c_void, b_dev: *const c_void, n: u64, out_mont_host: *mut c_void,
                                    hip_stream: *mut c_void) -> c_int;
     pub fn zk_poly_eval_device(f: c_int, coeffs_dev: *const c_void, n: u64, x_mont_host: *const c_void, out_mont_host: *mut c_void,
