@@ -51,10 +51,10 @@ __global__ void __launch_bounds__(64) batch_invert_kernel(Fe<F>* __restrict__ a,
 
 // ---- exclusive multiplicative scan ----
 // phase 1: workgroup b covers elements [b*4096, +4096): out[i] = product of the elements before i INSIDE the workgroup's
-// range; block_tot[b] = product of the whole range
+// range; block_tot[b] = product of the whole range.  in == out is allowed (every lane reads its 16 elements before it writes
+// them), so neither is __restrict__
 template <class F>
-__global__ void __launch_bounds__(SCAN_WG) scan_block_kernel(const Fe<F>* __restrict__ in, Fe<F>* __restrict__ out, Fe<F>* __restrict__ block_tot,
-                                                            uint64_t n) {
+__global__ void __launch_bounds__(SCAN_WG) scan_block_kernel(const Fe<F>* in, Fe<F>* out, Fe<F>* __restrict__ block_tot, uint64_t n) {
     __shared__ Fe<F> part[SCAN_WG];
     const uint32_t tid = threadIdx.x;
     const uint64_t lo = ((uint64_t)blockIdx.x * SCAN_WG + tid) * SCAN_K;
@@ -226,8 +226,9 @@ __global__ void __launch_bounds__(256) inner_product_kernel(const Fe<F>* __restr
 // a[i] = a[i] * s + b[i]: one Horner step of the multiopen combination (poly/multiopen/prover.rs: the polynomials queried at the
 // same point set are folded with powers of x_1, the per-set quotients with x_4) on resident coefficient vectors
 template <class F>
-__global__ void __launch_bounds__(256) vec_muladd_kernel(Fe<F>* out, const Fe<F>* a, const Fe<F>* __restrict__ b, uint64_t n, Fe<F> s) {
-    // out[i] = a[i] s + b[i]; out == a is the in-place Horner step (every lane reads its element before it writes it)
+__global__ void __launch_bounds__(256) vec_muladd_kernel(Fe<F>* out, const Fe<F>* a, const Fe<F>* b, uint64_t n, Fe<F> s) {
+    // out[i] = a[i] s + b[i]; out == a is the in-place Horner step, out == b allowed too (every lane reads its elements before it
+    // writes one): no pointer is __restrict__
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         Fe<F> x = a[i];
         const Fe<F> y = b[i];
@@ -257,9 +258,9 @@ __global__ void __launch_bounds__(64) pow_ladder_kernel(Fe<F> x, Fe<F>* __restri
 // fold of `count` resident polynomials in ONE pass -- every polynomial is read once and the result written once, where count - 1
 // muladd launches re-read and re-write the accumulator each time (3 x the traffic).  The multiopen argument folds every point
 // set's polynomials this way (powers of x_1), the vanishing argument the pieces of h (powers of x^n, last piece first).
+// out may be one of the sources (a lane reads all of its inputs before it writes), so it is not __restrict__.
 template <class F>
-__global__ void __launch_bounds__(256) vec_fold_many_kernel(Fe<F>* __restrict__ out, const Fe<F>* first, int64_t stride, uint32_t count, uint64_t n,
-                                                            Fe<F> s) {
+__global__ void __launch_bounds__(256) vec_fold_many_kernel(Fe<F>* out, const Fe<F>* first, int64_t stride, uint32_t count, uint64_t n, Fe<F> s) {
     for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (uint64_t)gridDim.x * blockDim.x) {
         const Fe<F>* p = first + j;
         Fe<F> acc = *p;
