@@ -25,17 +25,8 @@ CURVE_NAMES = {"Pallas": PALLAS, "Vesta": VESTA, "Bn254G1": BN254_G1, "Bls381G1"
                "Bn254G2": BN254_G2, "Bls381G2": BLS12_381_G2}
 FIELD_NAMES = {"PallasFp": FP_PALLAS, "PallasFq": FQ_PALLAS, "Bn254Fr": FR_BN254, "Bls381Fr": FR_BLS12_381}
 
-EXPORTS = [
-    "zk_init", "zk_shutdown", "zk_strerror", "zk_backend_info", "zk_field_limbs64", "zk_curve_base_limbs64",
-    "zk_curve_scalar_field", "zk_msm_window_bits", "zk_msm_window_count", "zk_bases_upload", "zk_bases_adopt_device",
-    "zk_bases_free", "zk_msm", "zk_msm_device", "zk_msm_last_profile", "zk_ntt", "zk_ntt_device", "zk_coset_mul",
-    "zk_coset_mul_device", "zk_ntt_coset_device", "zk_field_root_of_unity", "zk_field_multiplicative_generator", "zk_field_inverse",
-    "zk_point_add", "zk_point_to_affine", "zk_fixed_base_mul_device", "zk_vec_op_device", "zk_groth16_witness_map_device",
-    "zk_fixed_base_msm_device", "zk_ntt_extend_device", "zk_init_devices", "zk_device_count", "zk_msm_submit", "zk_msm_collect",
-    "zk_msm_batch_device", "zk_ntt_configure", "zk_msm_profile_totals", "zk_ntt_profile_enable", "zk_ntt_profile_read",
-    "zk_field_modulus", "zk_vec_scale_periodic_device", "zk_bases_refresh", "zk_bases_precompute", "zk_ntt_oop_device",
-    "zk_ntt_points_device", "zk_ntt_points",
-]
+# zk_status (include/zkcp_amd.h), the codes the package names
+ZK_ERR_INVALID_ARG, ZK_ERR_LOOKUP = -1, -9
 
 
 class ZkError(RuntimeError):
@@ -82,11 +73,74 @@ class NttTotals(ctypes.Structure):
                 ("algorithmic_bytes", ctypes.c_double)]
 
 
+i32, u32, i64, u64, vp, cp, ptr = (ctypes.c_int, ctypes.c_uint32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_char_p,
+                                   ctypes.POINTER)
+
+# The argument types of every function include/zkcp_amd.h declares: plain data, bound by load() and by nothing else.  A module
+# that wraps entry points of include/zkcp_amd_prover.h keeps their rows in a table of the same form (its SIGNATURES); a new
+# entry point needs its row in one of them (tests/test_py_abi.py holds every row against the headers).
+SIGNATURES = {
+    "zk_init": [i32],
+    "zk_init_devices": [i32, ptr(i32)],
+    "zk_device_count": [],
+    "zk_shutdown": [],
+    "zk_strerror": [i32],
+    "zk_backend_info": [cp, u64],
+    "zk_field_limbs64": [i32],
+    "zk_curve_base_limbs64": [i32],
+    "zk_curve_scalar_field": [i32],
+    "zk_bases_upload": [i32, vp, u64, ptr(u64)],
+    "zk_bases_adopt_device": [i32, vp, u64, ptr(u64)],
+    "zk_bases_free": [u64],
+    "zk_bases_refresh": [u64, u64, u64, vp],
+    "zk_bases_precompute": [u64, i32],
+    "zk_msm": [i32, u64, vp, u64, i32, ptr(MsmOpts), vp],
+    "zk_msm_device": [i32, u64, vp, u64, i32, ptr(MsmOpts), vp, vp],
+    "zk_msm_last_profile": [ptr(MsmProfile)],
+    "zk_msm_submit": [i32, u64, vp, u64, i32, ptr(MsmOpts), vp, ptr(u64)],
+    "zk_msm_collect": [u64, vp],
+    "zk_msm_batch_device": [i32, u64, vp, u64, u32, u64, i32, ptr(MsmOpts), vp, vp],
+    "zk_msm_profile_totals": [ptr(MsmTotals), i32],
+    "zk_msm_window_bits": [i32, u64, i32],
+    "zk_msm_window_count": [i32, u64, i32],
+    "zk_ntt_configure": [ptr(NttOpts)],
+    "zk_ntt_profile_enable": [i32],
+    "zk_ntt_profile_read": [ptr(NttTotals)],
+    "zk_ntt": [i32, vp, u32, vp, i32],
+    "zk_ntt_device": [i32, vp, u32, vp, i32, vp],
+    "zk_ntt_coset_device": [i32, vp, u32, vp, i32, vp, vp, vp],
+    "zk_ntt_extend_device": [i32, vp, u32, u32, vp, i32, vp, vp, vp],
+    "zk_ntt_oop_device": [i32, vp, vp, u32, u32, vp, i32, vp, vp, vp],
+    "zk_ntt_points_device": [i32, vp, vp, u32, vp, i32, vp],
+    "zk_ntt_points": [i32, vp, u32, vp, i32],
+    "zk_coset_mul": [i32, vp, u32, vp],
+    "zk_coset_mul_device": [i32, vp, u32, vp, vp],
+    "zk_field_modulus": [i32, vp],
+    "zk_field_root_of_unity": [i32, u32, vp],
+    "zk_field_multiplicative_generator": [i32, vp],
+    "zk_field_inverse": [i32, vp, vp],
+    "zk_point_add": [i32, vp, vp, vp],
+    "zk_point_to_affine": [i32, vp, vp],
+    "zk_fixed_base_mul_device": [i32, vp, u64, vp, vp],
+    "zk_fixed_base_msm_device": [i32, vp, vp, u64, i32, vp, vp],
+    "zk_vec_op_device": [i32, i32, vp, vp, vp, u64, vp, vp],
+    "zk_vec_scale_periodic_device": [i32, vp, u64, vp, u32, vp],
+    "zk_groth16_witness_map_device": [i32, vp, vp, vp, u32, vp],
+}
+# the two entry points of include/zkcp_amd_prover.h that `Bases` owns
+PROVER_SIGNATURES = {
+    "zk_bases_precompute_shifts": [i32, u64],
+    "zk_bases_shift_tables": [u64, ptr(u64)],
+}
+RETURNS = {"zk_strerror": cp}      # every other function returns its zk_status as an int
+EXPORTS = list(SIGNATURES)
+
 _lib = None
 
 
 def load(path=None):
-    """dlopen the HIP library (or, for the CPU test tier only, an explicitly given emulator build)."""
+    """dlopen the HIP library (or, for the CPU test tier only, an explicitly given emulator build) and bind every signature table
+    on that library object: whoever holds the handle calls typed functions"""
     global _lib
     if _lib is not None and path is None:
         return _lib
@@ -95,46 +149,11 @@ def load(path=None):
         raise RuntimeError("HIP extension %s is missing -- run `python contangle-zkcp_amd/build.py` "
                            "(there is no CPU fallback)" % p)
     lib = ctypes.CDLL(p)
-    lib.zk_strerror.restype = ctypes.c_char_p
-    u64, vp, i32 = ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int
-    lib.zk_bases_upload.argtypes = [i32, vp, u64, ctypes.POINTER(u64)]
-    lib.zk_bases_adopt_device.argtypes = [i32, vp, u64, ctypes.POINTER(u64)]
-    lib.zk_bases_free.argtypes = [u64]
-    lib.zk_bases_refresh.argtypes = [u64, u64, u64, vp]
-    lib.zk_bases_precompute.argtypes = [u64, i32]
-    lib.zk_msm.argtypes = [i32, u64, vp, u64, i32, ctypes.POINTER(MsmOpts), vp]
-    lib.zk_msm_device.argtypes = [i32, u64, vp, u64, i32, ctypes.POINTER(MsmOpts), vp, vp]
-    lib.zk_msm_last_profile.argtypes = [ctypes.POINTER(MsmProfile)]
-    lib.zk_msm_submit.argtypes = [i32, u64, vp, u64, i32, ctypes.POINTER(MsmOpts), vp, ctypes.POINTER(u64)]
-    lib.zk_msm_collect.argtypes = [u64, vp]
-    lib.zk_msm_batch_device.argtypes = [i32, u64, vp, u64, ctypes.c_uint32, u64, i32, ctypes.POINTER(MsmOpts), vp, vp]
-    lib.zk_init_devices.argtypes = [i32, ctypes.POINTER(i32)]
-    lib.zk_ntt_configure.argtypes = [ctypes.POINTER(NttOpts)]
-    lib.zk_msm_profile_totals.argtypes = [ctypes.POINTER(MsmTotals), i32]
-    lib.zk_ntt_profile_read.argtypes = [ctypes.POINTER(NttTotals)]
-    lib.zk_field_modulus.argtypes = [i32, vp]
-    lib.zk_vec_scale_periodic_device.argtypes = [i32, vp, u64, vp, ctypes.c_uint32, vp]
-    lib.zk_ntt.argtypes = [i32, vp, ctypes.c_uint32, vp, i32]
-    lib.zk_ntt_device.argtypes = [i32, vp, ctypes.c_uint32, vp, i32, vp]
-    lib.zk_ntt_coset_device.argtypes = [i32, vp, ctypes.c_uint32, vp, i32, vp, vp, vp]
-    lib.zk_ntt_extend_device.argtypes = [i32, vp, ctypes.c_uint32, ctypes.c_uint32, vp, i32, vp, vp, vp]
-    lib.zk_ntt_oop_device.argtypes = [i32, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, i32, vp, vp, vp]
-    lib.zk_ntt_points_device.argtypes = [i32, vp, vp, ctypes.c_uint32, vp, i32, vp]
-    lib.zk_ntt_points.argtypes = [i32, vp, ctypes.c_uint32, vp, i32]
-    lib.zk_coset_mul.argtypes = [i32, vp, ctypes.c_uint32, vp]
-    lib.zk_coset_mul_device.argtypes = [i32, vp, ctypes.c_uint32, vp, vp]
-    lib.zk_field_root_of_unity.argtypes = [i32, ctypes.c_uint32, vp]
-    lib.zk_field_multiplicative_generator.argtypes = [i32, vp]
-    lib.zk_field_inverse.argtypes = [i32, vp, vp]
-    lib.zk_point_add.argtypes = [i32, vp, vp, vp]
-    lib.zk_point_to_affine.argtypes = [i32, vp, vp]
-    lib.zk_fixed_base_mul_device.argtypes = [i32, vp, u64, vp, vp]
-    lib.zk_fixed_base_msm_device.argtypes = [i32, vp, vp, u64, i32, vp, vp]
-    lib.zk_vec_op_device.argtypes = [i32, i32, vp, vp, vp, u64, vp, vp]
-    lib.zk_groth16_witness_map_device.argtypes = [i32, vp, vp, vp, ctypes.c_uint32, vp]
-    lib.zk_msm_window_bits.argtypes = [i32, u64, i32]
-    lib.zk_msm_window_count.argtypes = [i32, u64, i32]
-    lib.zk_backend_info.argtypes = [ctypes.c_char_p, u64]
+    for table in (SIGNATURES, PROVER_SIGNATURES, ark_serialize.SIGNATURES, groth16.SIGNATURES, halo2.SIGNATURES, poseidon.SIGNATURES,
+                  encryption.SIGNATURES):
+        for name, argtypes in table.items():
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = argtypes, RETURNS.get(name, i32)
     _lib = lib
     return lib
 
@@ -148,14 +167,19 @@ def _check(status, what):
         raise ZkError(status, what)
 
 
+def _call(name, *args):
+    """call the entry point `name` of the loaded library; a status other than ZK_OK raises ZkError naming it"""
+    _check(getattr(load(), name)(*args), name)
+
+
 def init(device_id=0):
-    _check(load().zk_init(device_id), "zk_init")
+    _call("zk_init", device_id)
 
 
 def init_devices(device_ids):
     """one process drives several GPUs: bases go to every device, whole MSMs are split over them by scalar window"""
     ids = (ctypes.c_int * len(device_ids))(*device_ids)
-    _check(load().zk_init_devices(len(device_ids), ids), "zk_init_devices")
+    _call("zk_init_devices", len(device_ids), ids)
 
 
 def device_count():
@@ -166,7 +190,7 @@ def ntt_configure(max_log_radix=0, log_tile=None, block=0, limb_bits=0):
     """process-wide NTT plan knobs (tuning harness / tests); no arguments restores the defaults.
     limb_bits: 0 = lazy 29-bit limbs inside the tiles (default), 32 = saturated words"""
     o = NttOpts(max_log_radix, 0 if log_tile is None else log_tile + 1, block, limb_bits)
-    _check(load().zk_ntt_configure(ctypes.byref(o)), "zk_ntt_configure")
+    _call("zk_ntt_configure", ctypes.byref(o))
 
 
 def shutdown():
@@ -176,7 +200,7 @@ def shutdown():
 
 def backend_info():
     buf = ctypes.create_string_buffer(256)
-    _check(load().zk_backend_info(buf, 256), "zk_backend_info")
+    _call("zk_backend_info", buf, 256)
     return buf.value.decode()
 
 
@@ -212,40 +236,40 @@ def scalar_field(curve):
 def field_modulus(field):
     """the field's prime as a Python int"""
     out = np.zeros(4, dtype=np.uint64)
-    _check(load().zk_field_modulus(field_id(field), _ptr(out)), "zk_field_modulus")
+    _call("zk_field_modulus", field_id(field), _ptr(out))
     return sum(int(w) << (64 * i) for i, w in enumerate(out.tolist()))
 
 
 def root_of_unity(field, log_n):
     out = np.zeros(4, dtype=np.uint64)
-    _check(load().zk_field_root_of_unity(field_id(field), log_n, _ptr(out)), "zk_field_root_of_unity")
+    _call("zk_field_root_of_unity", field_id(field), log_n, _ptr(out))
     return out
 
 
 def multiplicative_generator(field):
     out = np.zeros(4, dtype=np.uint64)
-    _check(load().zk_field_multiplicative_generator(field_id(field), _ptr(out)), "zk_field_multiplicative_generator")
+    _call("zk_field_multiplicative_generator", field_id(field), _ptr(out))
     return out
 
 
 def field_inverse(field, a):
     a = _np64(a)
     out = np.zeros(4, dtype=np.uint64)
-    _check(load().zk_field_inverse(field_id(field), _ptr(a), _ptr(out)), "zk_field_inverse")
+    _call("zk_field_inverse", field_id(field), _ptr(a), _ptr(out))
     return out
 
 
 def point_add(curve, ja, jb):
     ja, jb = _np64(ja), _np64(jb)
     out = np.zeros_like(ja)
-    _check(load().zk_point_add(curve_id(curve), _ptr(ja), _ptr(jb), _ptr(out)), "zk_point_add")
+    _call("zk_point_add", curve_id(curve), _ptr(ja), _ptr(jb), _ptr(out))
     return out
 
 
 def point_to_affine(curve, jac):
     jac = _np64(jac)
     out = np.zeros(2 * (jac.shape[-1] // 3), dtype=np.uint64)
-    _check(load().zk_point_to_affine(curve_id(curve), _ptr(jac), _ptr(out)), "zk_point_to_affine")
+    _call("zk_point_to_affine", curve_id(curve), _ptr(jac), _ptr(out))
     return out
 
 
@@ -267,37 +291,34 @@ class Bases:
         if device_tensor is not None:
             self._keep = device_tensor
             self.n = int(n if n is not None else device_tensor.shape[0])
-            _check(load().zk_bases_adopt_device(self.curve, _ptr(device_tensor), self.n, ctypes.byref(h)),
-                   "zk_bases_adopt_device")
+            _call("zk_bases_adopt_device", self.curve, _ptr(device_tensor), self.n, ctypes.byref(h))
         else:
             pts = _np64(points)
             self.n = int(pts.shape[0])
-            _check(load().zk_bases_upload(self.curve, _ptr(pts), self.n, ctypes.byref(h)), "zk_bases_upload")
+            _call("zk_bases_upload", self.curve, _ptr(pts), self.n, ctypes.byref(h))
         self.handle = h.value
 
     def precompute(self, window_bits=0):
         """build the table of window multiples for msm(..., precomputed=True)"""
-        _check(load().zk_bases_precompute(self.handle, window_bits), "zk_bases_precompute")
+        _call("zk_bases_precompute", self.handle, window_bits)
 
     def precompute_shifts(self):
         """build the shift tables [2^64] P, [2^128] P, [2^192] P of the generator collapse (halo2.IpaProverVirtual.collapse): once,
         where the key is loaded -- otherwise the second collapse over a large handle builds them"""
-        from . import halo2
-        _check(halo2._plib().zk_bases_precompute_shifts(self.curve, self.handle), "zk_bases_precompute_shifts")
+        _call("zk_bases_precompute_shifts", self.curve, self.handle)
 
     def has_shift_tables(self):
-        from . import halo2
         out = ctypes.c_uint64(0)
-        _check(halo2._plib().zk_bases_shift_tables(self.handle, ctypes.byref(out)), "zk_bases_shift_tables")
+        _call("zk_bases_shift_tables", self.handle, ctypes.byref(out))
         return bool(out.value)
 
     def refresh(self, offset, count, stream=0):
         """points [offset, offset + count) of the adopted device buffer were rewritten on `stream`: update the derived copies"""
-        _check(load().zk_bases_refresh(self.handle, offset, count, ctypes.c_void_p(stream)), "zk_bases_refresh")
+        _call("zk_bases_refresh", self.handle, offset, count, ctypes.c_void_p(stream))
 
     def free(self):
         if self.handle:
-            _check(load().zk_bases_free(self.handle), "zk_bases_free")
+            _call("zk_bases_free", self.handle)
             self.handle = 0
 
     def __del__(self):
@@ -337,11 +358,10 @@ def msm(bases, scalars, montgomery=False, window_bits=0, windows=None, stream=0,
     if isinstance(scalars, np.ndarray):
         sc = _np64(scalars)
         n = int(sc.shape[0])
-        _check(lib.zk_msm(bases.curve, bases.handle, _ptr(sc), n, int(montgomery), ctypes.byref(opts), _ptr(out)), "zk_msm")
+        _call("zk_msm", bases.curve, bases.handle, _ptr(sc), n, int(montgomery), ctypes.byref(opts), _ptr(out))
     else:
         n = int(scalars.shape[0])
-        _check(lib.zk_msm_device(bases.curve, bases.handle, _ptr(scalars), n, int(montgomery), ctypes.byref(opts),
-                                 _ptr(out), ctypes.c_void_p(stream)), "zk_msm_device")
+        _call("zk_msm_device", bases.curve, bases.handle, _ptr(scalars), n, int(montgomery), ctypes.byref(opts), _ptr(out), ctypes.c_void_p(stream))
     return out
 
 
@@ -353,7 +373,7 @@ class MsmTicket:
 
     def collect(self):
         out = np.zeros(3 * self._nl, dtype=np.uint64)
-        _check(load().zk_msm_collect(self.ticket, _ptr(out)), "zk_msm_collect")
+        _call("zk_msm_collect", self.ticket, _ptr(out))
         self._keep = None
         return out
 
@@ -363,8 +383,8 @@ def msm_submit(bases, d_scalars, montgomery=False, window_bits=0, windows=None, 
     lib = load()
     opts = msm_opts(window_bits, windows, **tuning)
     t = ctypes.c_uint64(0)
-    _check(lib.zk_msm_submit(bases.curve, bases.handle, _ptr(d_scalars), int(d_scalars.shape[0]), int(montgomery), ctypes.byref(opts),
-                             ctypes.c_void_p(stream), ctypes.byref(t)), "zk_msm_submit")
+    _call("zk_msm_submit", bases.curve, bases.handle, _ptr(d_scalars), int(d_scalars.shape[0]), int(montgomery), ctypes.byref(opts),
+          ctypes.c_void_p(stream), ctypes.byref(t))
     return MsmTicket(t.value, lib.zk_curve_base_limbs64(bases.curve), d_scalars)
 
 
@@ -375,32 +395,32 @@ def msm_batch(bases, d_scalars, montgomery=False, window_bits=0, windows=None, s
     nl = lib.zk_curve_base_limbs64(bases.curve)
     out = np.zeros((count, 3 * nl), dtype=np.uint64)
     opts = msm_opts(window_bits, windows, **tuning)
-    _check(lib.zk_msm_batch_device(bases.curve, bases.handle, _ptr(d_scalars), n, count, n, int(montgomery), ctypes.byref(opts),
-                                   _ptr(out), ctypes.c_void_p(stream)), "zk_msm_batch_device")
+    _call("zk_msm_batch_device", bases.curve, bases.handle, _ptr(d_scalars), n, count, n, int(montgomery), ctypes.byref(opts), _ptr(out),
+          ctypes.c_void_p(stream))
     return out
 
 
 def msm_last_profile():
     p = MsmProfile()
-    _check(load().zk_msm_last_profile(ctypes.byref(p)), "zk_msm_last_profile")
+    _call("zk_msm_last_profile", ctypes.byref(p))
     return {k: getattr(p, k) for k, _ in MsmProfile._fields_}
 
 
 def msm_profile_totals(reset=True):
     """sums over every MSM collected since the last reset (batches, MSMs in flight)"""
     t = MsmTotals()
-    _check(load().zk_msm_profile_totals(ctypes.byref(t), int(reset)), "zk_msm_profile_totals")
+    _call("zk_msm_profile_totals", ctypes.byref(t), int(reset))
     return {k: getattr(t, k) for k, _ in MsmTotals._fields_}
 
 
 def ntt_profile_enable(on=True):
-    _check(load().zk_ntt_profile_enable(int(on)), "zk_ntt_profile_enable")
+    _call("zk_ntt_profile_enable", int(on))
 
 
 def ntt_profile_read():
     """waits for the bracketed ntt_pass_kernel launches since the last read; sums and resets"""
     t = NttTotals()
-    _check(load().zk_ntt_profile_read(ctypes.byref(t)), "zk_ntt_profile_read")
+    _call("zk_ntt_profile_read", ctypes.byref(t))
     return {k: getattr(t, k) for k, _ in NttTotals._fields_}
 
 
@@ -410,7 +430,6 @@ def ntt(field, a, omega, scale_by_n_inv=False, stream=0, coset_pre=None, coset_p
     device buffers.  device=True treats a numpy array as a device buffer (only meaningful under the CPU test emulator).
     in_log: the input is a[:2^in_log] zero-extended to len(a) (halo2 coeff_to_extended); the padding is never read.
     src (device buffers): read the input from there instead and leave it untouched -- the result lands in `a` (out of place)."""
-    lib = load()
     om = _np64(omega)
     if src is not None:
         n = int(a.shape[0])
@@ -420,9 +439,8 @@ def ntt(field, a, omega, scale_by_n_inv=False, stream=0, coset_pre=None, coset_p
         assert int(src.shape[0]) >= 1 << li
         gp = _np64(coset_pre) if coset_pre is not None else None
         gq = _np64(coset_post) if coset_post is not None else None
-        _check(lib.zk_ntt_oop_device(field_id(field), _ptr(src), _ptr(a), log_n, li, _ptr(om), int(scale_by_n_inv),
-                                     _ptr(gp) if gp is not None else None, _ptr(gq) if gq is not None else None,
-                                     ctypes.c_void_p(stream)), "zk_ntt_oop_device")
+        _call("zk_ntt_oop_device", field_id(field), _ptr(src), _ptr(a), log_n, li, _ptr(om), int(scale_by_n_inv),
+              _ptr(gp) if gp is not None else None, _ptr(gq) if gq is not None else None, ctypes.c_void_p(stream))
         return a
     if isinstance(a, np.ndarray) and not device and in_log is None:
         buf = _np64(a).copy()
@@ -430,10 +448,10 @@ def ntt(field, a, omega, scale_by_n_inv=False, stream=0, coset_pre=None, coset_p
         log_n = n.bit_length() - 1
         assert n == 1 << log_n
         if coset_pre is not None:
-            _check(lib.zk_coset_mul(field_id(field), _ptr(buf), log_n, _ptr(_np64(coset_pre))), "zk_coset_mul")
-        _check(lib.zk_ntt(field_id(field), _ptr(buf), log_n, _ptr(om), int(scale_by_n_inv)), "zk_ntt")
+            _call("zk_coset_mul", field_id(field), _ptr(buf), log_n, _ptr(_np64(coset_pre)))
+        _call("zk_ntt", field_id(field), _ptr(buf), log_n, _ptr(om), int(scale_by_n_inv))
         if coset_post is not None:
-            _check(lib.zk_coset_mul(field_id(field), _ptr(buf), log_n, _ptr(_np64(coset_post))), "zk_coset_mul")
+            _call("zk_coset_mul", field_id(field), _ptr(buf), log_n, _ptr(_np64(coset_post)))
         return buf
     n = int(a.shape[0])
     log_n = n.bit_length() - 1
@@ -441,19 +459,16 @@ def ntt(field, a, omega, scale_by_n_inv=False, stream=0, coset_pre=None, coset_p
     if in_log is not None:      # zero-extended input (device buffers): only a[:2^in_log] is read
         gp = _np64(coset_pre) if coset_pre is not None else None
         gq = _np64(coset_post) if coset_post is not None else None
-        _check(lib.zk_ntt_extend_device(field_id(field), _ptr(a), log_n, int(in_log), _ptr(om), int(scale_by_n_inv),
-                                        _ptr(gp) if gp is not None else None, _ptr(gq) if gq is not None else None,
-                                        ctypes.c_void_p(stream)), "zk_ntt_extend_device")
+        _call("zk_ntt_extend_device", field_id(field), _ptr(a), log_n, int(in_log), _ptr(om), int(scale_by_n_inv),
+              _ptr(gp) if gp is not None else None, _ptr(gq) if gq is not None else None, ctypes.c_void_p(stream))
         return a
     if coset_pre is None and coset_post is None:
-        _check(lib.zk_ntt_device(field_id(field), _ptr(a), log_n, _ptr(om), int(scale_by_n_inv), ctypes.c_void_p(stream)),
-               "zk_ntt_device")
+        _call("zk_ntt_device", field_id(field), _ptr(a), log_n, _ptr(om), int(scale_by_n_inv), ctypes.c_void_p(stream))
     else:
         gp = _np64(coset_pre) if coset_pre is not None else None
         gq = _np64(coset_post) if coset_post is not None else None
-        _check(lib.zk_ntt_coset_device(field_id(field), _ptr(a), log_n, _ptr(om), int(scale_by_n_inv),
-                                       _ptr(gp) if gp is not None else None, _ptr(gq) if gq is not None else None,
-                                       ctypes.c_void_p(stream)), "zk_ntt_coset_device")
+        _call("zk_ntt_coset_device", field_id(field), _ptr(a), log_n, _ptr(om), int(scale_by_n_inv), _ptr(gp) if gp is not None else None,
+              _ptr(gq) if gq is not None else None, ctypes.c_void_p(stream))
     return a
 
 
@@ -465,8 +480,7 @@ def ntt_points_device(curve, d_src, d_dst, log_n, omega, scale_by_n_inv=False, s
     (device buffers, Montgomery, identity = (0, 0); d_src may be d_dst): halo2 best_fft with G = the curve.  omega: a
     2^log_n-th root of unity of the curve's scalar field, Montgomery limbs on the host.  Does not synchronise."""
     om = _np64(omega)
-    _check(load().zk_ntt_points_device(curve_id(curve), _ptr(d_src), _ptr(d_dst), int(log_n), _ptr(om), int(bool(scale_by_n_inv)),
-                                       ctypes.c_void_p(stream)), "zk_ntt_points_device")
+    _call("zk_ntt_points_device", curve_id(curve), _ptr(d_src), _ptr(d_dst), int(log_n), _ptr(om), int(bool(scale_by_n_inv)), ctypes.c_void_p(stream))
     return d_dst
 
 
@@ -475,20 +489,19 @@ def ntt_points(curve, jacobian, log_n, omega, scale_by_n_inv=False):
     returns a new array with every z = 1 (Montgomery) or (0, 1, 0) for the identity"""
     buf = _np64(jacobian).copy()
     om = _np64(omega)
-    _check(load().zk_ntt_points(curve_id(curve), _ptr(buf), int(log_n), _ptr(om), int(bool(scale_by_n_inv))), "zk_ntt_points")
+    _call("zk_ntt_points", curve_id(curve), _ptr(buf), int(log_n), _ptr(om), int(bool(scale_by_n_inv)))
     return buf
 
 
 def coset_mul(field, a, g, stream=0):
-    lib = load()
     gm = _np64(g)
     if isinstance(a, np.ndarray):
         buf = _np64(a).copy()
         log_n = buf.shape[0].bit_length() - 1
-        _check(lib.zk_coset_mul(field_id(field), _ptr(buf), log_n, _ptr(gm)), "zk_coset_mul")
+        _call("zk_coset_mul", field_id(field), _ptr(buf), log_n, _ptr(gm))
         return buf
     log_n = int(a.shape[0]).bit_length() - 1
-    _check(lib.zk_coset_mul_device(field_id(field), _ptr(a), log_n, _ptr(gm), ctypes.c_void_p(stream)), "zk_coset_mul_device")
+    _call("zk_coset_mul_device", field_id(field), _ptr(a), log_n, _ptr(gm), ctypes.c_void_p(stream))
     return a
 
 
@@ -500,12 +513,11 @@ def vec_op(field, op, a, b=None, c=None, scalar=None, stream=0):
     n = int(a.shape[0])
     if op == "scale_periodic":      # a[i] *= b[i mod len(b)], b a small host table
         tbl = _np64(b)
-        _check(load().zk_vec_scale_periodic_device(field_id(field), _ptr(a), n, _ptr(tbl), int(tbl.shape[0]), ctypes.c_void_p(stream)),
-               "zk_vec_scale_periodic_device")
+        _call("zk_vec_scale_periodic_device", field_id(field), _ptr(a), n, _ptr(tbl), int(tbl.shape[0]), ctypes.c_void_p(stream))
         return a
     sp = _ptr(_np64(scalar)) if scalar is not None else None
-    _check(load().zk_vec_op_device(field_id(field), VEC_OPS[op], _ptr(a), _ptr(b) if b is not None else None,
-                                   _ptr(c) if c is not None else None, n, sp, ctypes.c_void_p(stream)), "zk_vec_op_device")
+    _call("zk_vec_op_device", field_id(field), VEC_OPS[op], _ptr(a), _ptr(b) if b is not None else None, _ptr(c) if c is not None else None, n, sp,
+          ctypes.c_void_p(stream))
     return a
 
 
@@ -514,23 +526,21 @@ def groth16_witness_map(field, a, b, c, stream=0):
     m = int(a.shape[0])
     log_m = m.bit_length() - 1
     assert m == 1 << log_m and int(b.shape[0]) == m and int(c.shape[0]) == m
-    _check(load().zk_groth16_witness_map_device(field_id(field), _ptr(a), _ptr(b), _ptr(c), log_m, ctypes.c_void_p(stream)),
-           "zk_groth16_witness_map_device")
+    _call("zk_groth16_witness_map_device", field_id(field), _ptr(a), _ptr(b), _ptr(c), log_m, ctypes.c_void_p(stream))
     return a
 
 
 def fixed_base_mul_device(curve, d_scalars, d_out, n, stream=0):
-    _check(load().zk_fixed_base_mul_device(curve_id(curve), _ptr(d_scalars), n, _ptr(d_out), ctypes.c_void_p(stream)),
-           "zk_fixed_base_mul_device")
+    _call("zk_fixed_base_mul_device", curve_id(curve), _ptr(d_scalars), n, _ptr(d_out), ctypes.c_void_p(stream))
 
 
 def fixed_base_msm_device(curve, d_scalars, d_out, n, base=None, montgomery=False, stream=0):
     """d_out[i] = [k_i] base (affine); base: numpy uint64 (x, y) Montgomery limbs on the host, None = the generator."""
     b = _np64(base) if base is not None else None
-    _check(load().zk_fixed_base_msm_device(curve_id(curve), _ptr(b) if b is not None else None, _ptr(d_scalars), n, int(montgomery),
-                                           _ptr(d_out), ctypes.c_void_p(stream)), "zk_fixed_base_msm_device")
+    _call("zk_fixed_base_msm_device", curve_id(curve), _ptr(b) if b is not None else None, _ptr(d_scalars), n, int(montgomery), _ptr(d_out),
+          ctypes.c_void_p(stream))
 
 
 from . import ark, ark_serialize, groth16, halo2, poseidon, jubjub, r1cs, encryption  # noqa: E402,F401  (interface mirrors)
 
-PROVER_EXPORTS = groth16.PROVER_EXPORTS + halo2.PROVER_EXPORTS + poseidon.PROVER_EXPORTS + encryption.PROVER_EXPORTS
+PROVER_EXPORTS = list(PROVER_SIGNATURES) + groth16.PROVER_EXPORTS + halo2.PROVER_EXPORTS + poseidon.PROVER_EXPORTS + encryption.PROVER_EXPORTS

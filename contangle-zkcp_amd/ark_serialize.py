@@ -16,16 +16,11 @@ import json
 
 import numpy as np
 
-from . import Bases, ZkError, _check, _np64, _ptr, base_limbs, curve_id, load
+from . import Bases, ZkError, _call, _np64, _ptr, base_limbs, cp, curve_id, field_id, i32, load, ptr, u64, vp
 
 BN254, BLS12_381 = 0, 1
 PAIRING_NAMES = {"Bn254": BN254, "Bls381": BLS12_381}
 PAIRING_CURVES = {BN254: ("Bn254G1", "Bn254G2"), BLS12_381: ("Bls381G1", "Bls381G2")}
-
-PROVER_EXPORTS = ["zk_ark_point_size", "zk_ark_points_encode", "zk_ark_points_decode", "zk_ark_scalars_encode", "zk_ark_scalars_decode",
-                  "zk_ark_proving_key_index", "zk_bases_upload_ark", "zk_ark_proof_size", "zk_ark_proof_encode", "zk_ark_proof_decode",
-                  "zk_ark_points_decode_checked", "zk_ark_points_decode_checked_device"]
-
 
 class Span(ctypes.Structure):
     _fields_ = [("offset", ctypes.c_uint64), ("count", ctypes.c_uint64)]
@@ -45,20 +40,22 @@ def pairing_id(p):
     return PAIRING_NAMES[p] if isinstance(p, str) else p
 
 
-def _lib():
-    lib = load()
-    u8p, u64, vp, i32 = ctypes.c_char_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int
-    lib.zk_ark_points_encode.argtypes = [i32, vp, u64, i32, vp]
-    lib.zk_ark_points_decode.argtypes = [i32, u8p, u64, i32, i32, vp]
-    lib.zk_ark_scalars_encode.argtypes = [i32, vp, u64, vp]
-    lib.zk_ark_scalars_decode.argtypes = [i32, u8p, u64, vp]
-    lib.zk_ark_proving_key_index.argtypes = [i32, u8p, u64, ctypes.POINTER(PkIndex)]
-    lib.zk_bases_upload_ark.argtypes = [i32, u8p, u64, ctypes.POINTER(u64)]
-    lib.zk_ark_proof_encode.argtypes = [i32, vp, vp, vp, vp]
-    lib.zk_ark_proof_decode.argtypes = [i32, u8p, vp, vp, vp]
-    lib.zk_ark_points_decode_checked.argtypes = [i32, u8p, u64, i32, vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
-    lib.zk_ark_points_decode_checked_device.argtypes = [i32, u8p, u64, i32, vp, ctypes.POINTER(u64), ctypes.POINTER(u64), vp]
-    return lib
+SIGNATURES = {
+    "zk_ark_point_size": [i32, i32],
+    "zk_ark_points_encode": [i32, vp, u64, i32, vp],
+    "zk_ark_points_decode": [i32, cp, u64, i32, i32, vp],
+    "zk_ark_scalars_encode": [i32, vp, u64, vp],
+    "zk_ark_scalars_decode": [i32, cp, u64, vp],
+    "zk_ark_proving_key_index": [i32, cp, u64, ptr(PkIndex)],
+    "zk_bases_upload_ark": [i32, cp, u64, ptr(u64)],
+    "zk_ark_proof_size": [i32],
+    "zk_ark_proof_encode": [i32, vp, vp, vp, vp],
+    "zk_ark_proof_decode": [i32, cp, vp, vp, vp],
+    "zk_ark_points_decode_checked": [i32, cp, u64, i32, vp, ptr(u64), ptr(u64)],
+    "zk_ark_points_decode_checked_device": [i32, cp, u64, i32, vp, ptr(u64), ptr(u64), vp],
+}
+PROVER_EXPORTS = list(SIGNATURES)
+_lib = load         # the bound handle (tests and tools take it for raw calls)
 
 
 def point_size(curve, compressed=True):
@@ -69,13 +66,13 @@ def points_to_bytes(curve, pts, compressed=True):
     """GroupAffine::serialize (compressed) / serialize_uncompressed for each point, concatenated (no length prefix)"""
     pts = _np64(pts).reshape(-1, 2 * base_limbs(curve))
     out = np.zeros(pts.shape[0] * point_size(curve, compressed), dtype=np.uint8)
-    _check(_lib().zk_ark_points_encode(curve_id(curve), _ptr(pts), pts.shape[0], int(compressed), _ptr(out)), "zk_ark_points_encode")
+    _call("zk_ark_points_encode", curve_id(curve), _ptr(pts), pts.shape[0], int(compressed), _ptr(out))
     return out.tobytes()
 
 
 def points_from_bytes(curve, buf, n, compressed=True, check_on_curve=False):
     out = np.zeros((n, 2 * base_limbs(curve)), dtype=np.uint64)
-    _check(_lib().zk_ark_points_decode(curve_id(curve), bytes(buf), n, int(compressed), int(check_on_curve), _ptr(out)), "zk_ark_points_decode")
+    _call("zk_ark_points_decode", curve_id(curve), bytes(buf), n, int(compressed), int(check_on_curve), _ptr(out))
     return out
 
 
@@ -126,17 +123,15 @@ def vec_to_bytes(curve, pts, compressed=True):
 
 
 def scalars_to_bytes(field, a):
-    from . import field_id
     a = _np64(a).reshape(-1, 4)
     out = np.zeros(a.shape[0] * 32, dtype=np.uint8)
-    _check(_lib().zk_ark_scalars_encode(field_id(field), _ptr(a), a.shape[0], _ptr(out)), "zk_ark_scalars_encode")
+    _call("zk_ark_scalars_encode", field_id(field), _ptr(a), a.shape[0], _ptr(out))
     return out.tobytes()
 
 
 def scalars_from_bytes(field, buf, n):
-    from . import field_id
     out = np.zeros((n, 4), dtype=np.uint64)
-    _check(_lib().zk_ark_scalars_decode(field_id(field), bytes(buf), n, _ptr(out)), "zk_ark_scalars_decode")
+    _call("zk_ark_scalars_decode", field_id(field), bytes(buf), n, _ptr(out))
     return out
 
 
@@ -150,7 +145,7 @@ class ProvingKey:
     @classmethod
     def deserialize_unchecked(cls, pairing, buf):
         idx = PkIndex()
-        _check(_lib().zk_ark_proving_key_index(pairing_id(pairing), bytes(buf), len(buf), ctypes.byref(idx)), "zk_ark_proving_key_index")
+        _call("zk_ark_proving_key_index", pairing_id(pairing), bytes(buf), len(buf), ctypes.byref(idx))
         if idx.total_bytes != len(buf):
             raise ValueError("trailing bytes after the proving key")
         return cls(pairing, buf, idx)
@@ -176,7 +171,7 @@ class ProvingKey:
         n = int(sp.count) - skip_first
         h = ctypes.c_uint64(0)
         start = sp.offset + skip_first * ps
-        _check(_lib().zk_bases_upload_ark(curve_id(c), self.buf[start: start + n * ps], n, ctypes.byref(h)), "zk_bases_upload_ark")
+        _call("zk_bases_upload_ark", curve_id(c), self.buf[start: start + n * ps], n, ctypes.byref(h))
         b = Bases.__new__(Bases)
         b.curve, b.n, b.handle, b._keep = curve_id(c), n, h.value, None
         return b
@@ -227,7 +222,7 @@ def proof_to_bytes(pairing, a, b, c):
     pairing = pairing_id(pairing)
     lib = _lib()
     out = np.zeros(lib.zk_ark_proof_size(pairing), dtype=np.uint8)
-    _check(lib.zk_ark_proof_encode(pairing, _ptr(_np64(a)), _ptr(_np64(b)), _ptr(_np64(c)), _ptr(out)), "zk_ark_proof_encode")
+    _call("zk_ark_proof_encode", pairing, _ptr(_np64(a)), _ptr(_np64(b)), _ptr(_np64(c)), _ptr(out))
     return out.tobytes()
 
 
@@ -238,7 +233,7 @@ def proof_from_bytes(pairing, buf):
                np.zeros(2 * base_limbs(g1), dtype=np.uint64))
     if len(buf) != _lib().zk_ark_proof_size(pairing):
         raise ValueError("wrong proof length")
-    _check(_lib().zk_ark_proof_decode(pairing, bytes(buf), _ptr(a), _ptr(b), _ptr(c)), "zk_ark_proof_decode")
+    _call("zk_ark_proof_decode", pairing, bytes(buf), _ptr(a), _ptr(b), _ptr(c))
     return a, b, c
 
 

@@ -23,21 +23,18 @@ import ctypes
 
 import numpy as np
 
-from . import _check, _ptr, field_id, jubjub, load, poseidon, r1cs
+from . import _call, _ptr, field_id, i32, jubjub, load, poseidon, r1cs, u64, vp
 from .groth16 import R1csMatrix, _new_buffer, _on_emulator, _upload
 
-PROVER_EXPORTS = ["zk_encrypt_witness_device", "zk_plaintext_from_bytes_device"]
+SIGNATURES = {
+    "zk_encrypt_witness_device": [i32, vp, u64, u64, vp, vp, vp, vp, vp, vp],
+    "zk_plaintext_from_bytes_device": [i32, vp, u64, vp, u64, vp],
+}
+PROVER_EXPORTS = list(SIGNATURES)
+_elib = load        # the bound handle (tests and tools take it for raw calls)
 
 FIELD = "Bls381Fr"
 _MASK64 = (1 << 64) - 1
-
-
-def _elib():
-    lib = load()
-    u64, vp, i32 = ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int
-    lib.zk_encrypt_witness_device.argtypes = [i32, vp, u64, u64, vp, vp, vp, vp, vp, vp]
-    lib.zk_plaintext_from_bytes_device.argtypes = [i32, vp, u64, vp, u64, vp]
-    return lib
 
 
 class Parameters:
@@ -99,8 +96,8 @@ def bytes_to_plaintext_chunks_direct(data, size, stream=0):
             d_bytes = torch.from_numpy(host).cuda()
     else:
         d_bytes = None
-    _check(_elib().zk_plaintext_from_bytes_device(field_id(FIELD), _ptr(d_bytes) if d_bytes is not None else None, len(data), _ptr(out), int(size),
-                                                 ctypes.c_void_p(stream)), "zk_plaintext_from_bytes_device")
+    _call("zk_plaintext_from_bytes_device", field_id(FIELD), _ptr(d_bytes) if d_bytes is not None else None, len(data), _ptr(out), int(size),
+          ctypes.c_void_p(stream))
     if d_bytes is not None and not _on_emulator():
         import torch
         torch.cuda.synchronize()        # d_bytes goes out of scope here
@@ -110,8 +107,8 @@ def bytes_to_plaintext_chunks_direct(data, size, stream=0):
 def encrypt_witness(msg_dev, msg_len, n, dh, c2_dev, m_dev, b_dev, k_dev, stream=0):
     """zk_encrypt_witness_device over Bls381Fr: the four per-element segments from the plaintext and dh (an integer)"""
     s = poseidon.to_mont(jubjub.P, [dh])
-    _check(_elib().zk_encrypt_witness_device(field_id(FIELD), _ptr(msg_dev) if msg_len else None, int(msg_len), int(n), _ptr(s), _ptr(c2_dev), _ptr(m_dev),
-                                            _ptr(b_dev), _ptr(k_dev), ctypes.c_void_p(stream)), "zk_encrypt_witness_device")
+    _call("zk_encrypt_witness_device", field_id(FIELD), _ptr(msg_dev) if msg_len else None, int(msg_len), int(n), _ptr(s), _ptr(c2_dev), _ptr(m_dev),
+          _ptr(b_dev), _ptr(k_dev), ctypes.c_void_p(stream))
 
 
 class EncryptCircuit:

@@ -23,14 +23,8 @@ import secrets
 
 import numpy as np
 
-from . import (Bases, _check, _np64, _ptr, ark_serialize, backend_info, base_limbs, curve_id, field_id, field_modulus, fixed_base_msm_device, load,
-               msm_submit, vec_op)
-
-PROVER_EXPORTS = ["zk_r1cs_matrix_upload", "zk_r1cs_matrix_free", "zk_r1cs_matvec_device", "zk_groth16_witness_map_r1cs_device",
-                  "zk_groth16_assemble_proof", "zk_r1cs_matvec_transposed_device", "zk_lagrange_coefficients_device",
-                  "zk_groth16_qap_at_device", "zk_groth16_key_scalars_device", "zk_pairing_product", "zk_groth16_verify",
-                  "zk_groth16_prepare_inputs", "zk_r1cs_first_unsatisfied_device"]
-
+from . import (Bases, _call, _np64, _ptr, ark_serialize, backend_info, base_limbs, curve_id, field_id, field_modulus, fixed_base_msm_device, i32,
+               load, msm_submit, ptr, u32, u64, vec_op, vp)
 
 class Assembly(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "delta_g2", "a_query0", "b_g1_query0",
@@ -41,23 +35,23 @@ class VkPoints(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2")]
 
 
-def _lib():
-    lib = load()
-    u64, vp, i32 = ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int
-    lib.zk_r1cs_matrix_upload.argtypes = [i32, vp, vp, vp, u64, u64, ctypes.POINTER(u64)]
-    lib.zk_r1cs_matrix_free.argtypes = [u64]
-    lib.zk_r1cs_matvec_device.argtypes = [u64, vp, vp, u64, vp]
-    lib.zk_groth16_witness_map_r1cs_device.argtypes = [i32, u64, u64, u64, vp, u64, ctypes.c_uint32, vp, vp, vp, vp]
-    lib.zk_groth16_assemble_proof.argtypes = [i32, ctypes.POINTER(Assembly), vp, vp, vp]
-    lib.zk_r1cs_matvec_transposed_device.argtypes = [u64, vp, u64, vp, u64, vp]
-    lib.zk_lagrange_coefficients_device.argtypes = [i32, ctypes.c_uint32, vp, vp, vp, vp]
-    lib.zk_groth16_qap_at_device.argtypes = [i32, u64, u64, u64, u64, ctypes.c_uint32, vp, vp, vp, vp, u64, vp, vp]
-    lib.zk_groth16_key_scalars_device.argtypes = [i32, vp, vp, vp, u64, u64, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.zk_pairing_product.argtypes = [i32, vp, vp, u64, vp]
-    lib.zk_groth16_verify.argtypes = [i32, ctypes.POINTER(VkPoints), vp, vp, vp, vp, vp, ctypes.POINTER(u64)]
-    lib.zk_groth16_prepare_inputs.argtypes = [i32, u64, vp, u64, vp, u64, vp, vp]
-    lib.zk_r1cs_first_unsatisfied_device.argtypes = [i32, u64, u64, u64, vp, u64, vp, u64, ctypes.POINTER(u64), vp]
-    return lib
+SIGNATURES = {
+    "zk_r1cs_matrix_upload": [i32, vp, vp, vp, u64, u64, ptr(u64)],
+    "zk_r1cs_matrix_free": [u64],
+    "zk_r1cs_matvec_device": [u64, vp, vp, u64, vp],
+    "zk_groth16_witness_map_r1cs_device": [i32, u64, u64, u64, vp, u64, u32, vp, vp, vp, vp],
+    "zk_groth16_assemble_proof": [i32, ptr(Assembly), vp, vp, vp],
+    "zk_r1cs_matvec_transposed_device": [u64, vp, u64, vp, u64, vp],
+    "zk_lagrange_coefficients_device": [i32, u32, vp, vp, vp, vp],
+    "zk_groth16_qap_at_device": [i32, u64, u64, u64, u64, u32, vp, vp, vp, vp, u64, vp, vp],
+    "zk_groth16_key_scalars_device": [i32, vp, vp, vp, u64, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "zk_pairing_product": [i32, vp, vp, u64, vp],
+    "zk_groth16_verify": [i32, ptr(VkPoints), vp, vp, vp, vp, vp, ptr(u64)],
+    "zk_groth16_prepare_inputs": [i32, u64, vp, u64, vp, u64, vp, vp],
+    "zk_r1cs_first_unsatisfied_device": [i32, u64, u64, u64, vp, u64, vp, u64, ptr(u64), vp],
+}
+PROVER_EXPORTS = list(SIGNATURES)
+_lib = load         # the bound handle (tests and tools take it for raw calls)
 
 
 class R1csMatrix:
@@ -83,26 +77,23 @@ class R1csMatrix:
                                  _np64(csr[2]))
         self.n_rows, self.n_cols = int(row_ptr.shape[0]) - 1, int(n_cols)
         h = ctypes.c_uint64(0)
-        _check(_lib().zk_r1cs_matrix_upload(self.field, _ptr(row_ptr), _ptr(col), _ptr(val), self.n_rows, self.n_cols, ctypes.byref(h)),
-               "zk_r1cs_matrix_upload")
+        _call("zk_r1cs_matrix_upload", self.field, _ptr(row_ptr), _ptr(col), _ptr(val), self.n_rows, self.n_cols, ctypes.byref(h))
         self.handle = h.value
 
     def matvec(self, d_z, d_out, stream=0):
-        _check(_lib().zk_r1cs_matvec_device(self.handle, _ptr(d_z), _ptr(d_out), int(d_out.shape[0]), ctypes.c_void_p(stream)),
-               "zk_r1cs_matvec_device")
+        _call("zk_r1cs_matvec_device", self.handle, _ptr(d_z), _ptr(d_out), int(d_out.shape[0]), ctypes.c_void_p(stream))
         return d_out
 
     def matvec_transposed(self, d_x, d_out, x_len=None, stream=0):
         """d_out[j] = sum_i M[i][j] d_x[i] over the rows i < x_len (default: all of d_x); d_out[n_cols:] = 0.  The first call on a
         matrix builds its column-major companion on the device."""
         x_len = int(d_x.shape[0]) if x_len is None else int(x_len)
-        _check(_lib().zk_r1cs_matvec_transposed_device(self.handle, _ptr(d_x), x_len, _ptr(d_out), int(d_out.shape[0]), ctypes.c_void_p(stream)),
-               "zk_r1cs_matvec_transposed_device")
+        _call("zk_r1cs_matvec_transposed_device", self.handle, _ptr(d_x), x_len, _ptr(d_out), int(d_out.shape[0]), ctypes.c_void_p(stream))
         return d_out
 
     def free(self):
         if self.handle:
-            _check(_lib().zk_r1cs_matrix_free(self.handle), "zk_r1cs_matrix_free")
+            _call("zk_r1cs_matrix_free", self.handle)
             self.handle = 0
 
 
@@ -112,9 +103,8 @@ def witness_map(field, A, B, C, d_z, num_inputs, d_a, d_b, d_c, stream=0):
     m = int(d_a.shape[0])
     log_m = m.bit_length() - 1
     assert m == 1 << log_m and int(d_b.shape[0]) == m and int(d_c.shape[0]) == m
-    _check(_lib().zk_groth16_witness_map_r1cs_device(field_id(field), A.handle, B.handle, C.handle, _ptr(d_z), num_inputs, log_m,
-                                                     _ptr(d_a), _ptr(d_b), _ptr(d_c), ctypes.c_void_p(stream)),
-           "zk_groth16_witness_map_r1cs_device")
+    _call("zk_groth16_witness_map_r1cs_device", field_id(field), A.handle, B.handle, C.handle, _ptr(d_z), num_inputs, log_m, _ptr(d_a), _ptr(d_b),
+          _ptr(d_c), ctypes.c_void_p(stream))
     return d_a
 
 
@@ -126,9 +116,8 @@ def first_unsatisfied(A, B, C, d_z, stream=0):
     assignment d_z (device buffer, canonical Montgomery) satisfies every row.  Synchronises the stream."""
     d_scratch = _new_buffer((3 * A.n_rows + R1CS_CHECK_SCRATCH_ELEMS, 4))
     row = ctypes.c_uint64(0)
-    _check(_lib().zk_r1cs_first_unsatisfied_device(A.field, A.handle, B.handle, C.handle, _ptr(d_z), int(d_z.shape[0]), _ptr(d_scratch),
-                                                   int(d_scratch.shape[0]), ctypes.byref(row), ctypes.c_void_p(stream)),
-           "zk_r1cs_first_unsatisfied_device")
+    _call("zk_r1cs_first_unsatisfied_device", A.field, A.handle, B.handle, C.handle, _ptr(d_z), int(d_z.shape[0]), _ptr(d_scratch),
+          int(d_scratch.shape[0]), ctypes.byref(row), ctypes.c_void_p(stream))
     return None if row.value == (1 << 64) - 1 else row.value
 
 
@@ -141,7 +130,7 @@ def assemble_proof(pairing, key_points, accs, r, s):
     asm = Assembly(**{k: ctypes.cast(_ptr(keep[k]), ctypes.c_void_p) for k, _ in Assembly._fields_})
     a, b, c = (np.zeros(2 * base_limbs(g1), dtype=np.uint64), np.zeros(2 * base_limbs(g2), dtype=np.uint64),
                np.zeros(2 * base_limbs(g1), dtype=np.uint64))
-    _check(_lib().zk_groth16_assemble_proof(pairing, ctypes.byref(asm), _ptr(a), _ptr(b), _ptr(c)), "zk_groth16_assemble_proof")
+    _call("zk_groth16_assemble_proof", pairing, ctypes.byref(asm), _ptr(a), _ptr(b), _ptr(c))
     return a, b, c
 
 
@@ -200,8 +189,7 @@ class Prover:
 def lagrange_coefficients(field, log_m, tau, d_out, stream=0):
     """d_out[i] = L_i(tau) on the size-2^log_m domain (evaluate_all_lagrange_coefficients); returns zt = tau^m - 1 (Montgomery limbs)"""
     zt = np.zeros(4, dtype=np.uint64)
-    _check(_lib().zk_lagrange_coefficients_device(field_id(field), int(log_m), _ptr(_np64(tau)), _ptr(d_out), _ptr(zt), ctypes.c_void_p(stream)),
-           "zk_lagrange_coefficients_device")
+    _call("zk_lagrange_coefficients_device", field_id(field), int(log_m), _ptr(_np64(tau)), _ptr(d_out), _ptr(zt), ctypes.c_void_p(stream))
     return zt
 
 
@@ -211,18 +199,16 @@ def qap_at(field, A, B, C, num_inputs, log_m, tau, d_u, d_v, d_w, stream=0):
     zt = np.zeros(4, dtype=np.uint64)
     n_vars = int(d_u.shape[0])
     assert int(d_v.shape[0]) == n_vars and int(d_w.shape[0]) == n_vars
-    _check(_lib().zk_groth16_qap_at_device(field_id(field), A.handle, B.handle, C.handle, int(num_inputs), int(log_m), _ptr(_np64(tau)),
-                                           _ptr(d_u), _ptr(d_v), _ptr(d_w), n_vars, _ptr(zt), ctypes.c_void_p(stream)),
-           "zk_groth16_qap_at_device")
+    _call("zk_groth16_qap_at_device", field_id(field), A.handle, B.handle, C.handle, int(num_inputs), int(log_m), _ptr(_np64(tau)), _ptr(d_u),
+          _ptr(d_v), _ptr(d_w), n_vars, _ptr(zt), ctypes.c_void_p(stream))
     return zt
 
 
 def key_scalars(field, d_u, d_v, d_w, num_inputs, log_m, alpha, beta, gamma, delta, tau, zt, d_abc, d_h, stream=0):
     """d_abc = (beta u + alpha v + w) / gamma for the inputs, / delta for the rest; d_h[i] = tau^i zt / delta, i < 2^log_m - 1"""
     sc = [_np64(x) for x in (alpha, beta, gamma, delta, tau, zt)]
-    _check(_lib().zk_groth16_key_scalars_device(field_id(field), _ptr(d_u), _ptr(d_v), _ptr(d_w), int(d_u.shape[0]), int(num_inputs), int(log_m),
-                                                *[_ptr(x) for x in sc], _ptr(d_abc), _ptr(d_h) if int(d_h.shape[0]) else None,
-                                                ctypes.c_void_p(stream)), "zk_groth16_key_scalars_device")
+    _call("zk_groth16_key_scalars_device", field_id(field), _ptr(d_u), _ptr(d_v), _ptr(d_w), int(d_u.shape[0]), int(num_inputs), int(log_m),
+          *[_ptr(x) for x in sc], _ptr(d_abc), _ptr(d_h) if int(d_h.shape[0]) else None, ctypes.c_void_p(stream))
     return d_abc, d_h
 
 
@@ -359,7 +345,7 @@ def pairing_product(pairing, g1_points, g2_points):
     a, b = _np64(g1_points).reshape(-1, 2 * base_limbs(c1)), _np64(g2_points).reshape(-1, 2 * base_limbs(c2))
     assert a.shape[0] == b.shape[0]
     out = np.zeros((12, base_limbs(c1)), dtype=np.uint64)
-    _check(_lib().zk_pairing_product(pairing, _ptr(a), _ptr(b), a.shape[0], _ptr(out)), "zk_pairing_product")
+    _call("zk_pairing_product", pairing, _ptr(a), _ptr(b), a.shape[0], _ptr(out))
     return out
 
 
@@ -433,9 +419,8 @@ def prepare_inputs(pvk, public_inputs, stream=0):
     if n_in + 1 != vk.n:
         raise MalformedVerifyingKey("%d public inputs for a key with %d gamma_abc_g1 points" % (n_in, vk.n))
     out = np.zeros(2 * base_limbs(vk.g1), dtype=np.uint64)
-    _check(_lib().zk_groth16_prepare_inputs(curve_id(vk.g1),
-                                            vk.tail.handle if vk.tail is not None else 0, _ptr(vk.gamma_abc0), vk.n,
-                                            _ptr(d_x) if n_in else None, n_in, _ptr(out), ctypes.c_void_p(stream)), "zk_groth16_prepare_inputs")
+    _call("zk_groth16_prepare_inputs", curve_id(vk.g1), vk.tail.handle if vk.tail is not None else 0, _ptr(vk.gamma_abc0), vk.n,
+          _ptr(d_x) if n_in else None, n_in, _ptr(out), ctypes.c_void_p(stream))
     return out
 
 
@@ -447,8 +432,7 @@ def verify_proof_with_prepared_inputs(pvk, proof, g_ic):
     pts = VkPoints(*[ctypes.cast(_ptr(x), ctypes.c_void_p) for x in (vk.alpha_g1, vk.beta_g2, vk.gamma_g2, vk.delta_g2)])
     ab = _np64(pvk.alpha_g1_beta_g2)
     ok = ctypes.c_uint64(0)
-    _check(_lib().zk_groth16_verify(vk.pairing, ctypes.byref(pts), _ptr(ab), _ptr(g_ic), _ptr(a), _ptr(b), _ptr(c), ctypes.byref(ok)),
-           "zk_groth16_verify")
+    _call("zk_groth16_verify", vk.pairing, ctypes.byref(pts), _ptr(ab), _ptr(g_ic), _ptr(a), _ptr(b), _ptr(c), ctypes.byref(ok))
     return bool(ok.value)
 
 

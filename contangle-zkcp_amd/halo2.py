@@ -14,18 +14,9 @@ import ctypes
 
 import numpy as np
 
-from . import (Bases, ZkError, _check, _np64, _ptr, base_limbs, curve_id, field_id, field_inverse, field_modulus, load, msm, msm_batch, msm_submit,
-               multiplicative_generator, ntt, ntt_points_device, root_of_unity, scalar_field, vec_op)
-
-PROVER_EXPORTS = ["zk_batch_invert_device", "zk_prefix_product_device", "zk_halo2_permutation_product_device",
-                  "zk_halo2_lookup_product_device", "zk_halo2_permute_expression_pair_device", "zk_inner_product_device", "zk_vec_fold_device", "zk_ipa_fold_bases_device",
-                  "zk_expr_eval_device", "zk_ipa_virtual_scalars_device", "zk_ipa_update_weights_device", "zk_ipa_collapse_device", "zk_ipa_collapse_range_device", "zk_ipa_round_device", "zk_bases_precompute_shifts", "zk_bases_shift_tables",
-                  "zk_poly_eval_device", "zk_poly_eval_batch_device", "zk_vec_muladd_device", "zk_vec_muladd_to_device", "zk_kate_division_device", "zk_vec_powers_device", "zk_vec_fold_many_device",
-                  "zk_ipa_fold_round_device", "zk_expr_eval_lazy_device", "zk_expr_configure", "zk_expr_specialised_source",
-                  "zk_halo2_assembly_new", "zk_halo2_assembly_copy", "zk_halo2_assembly_mapping", "zk_halo2_assembly_free",
-                  "zk_halo2_permutation_sigmas_device", "zk_halo2_ipa_s_device", "zk_halo2_ipa_compute_b",
-                  "zk_halo2_mock_eval_device", "zk_halo2_mock_lookup_device", "zk_halo2_mock_permutation_device", "zk_halo2_mock_failures_device"]
-
+from . import (ZK_ERR_INVALID_ARG, ZK_ERR_LOOKUP, Bases, ZkError, _call, _check, _np64, _ptr, base_limbs, cp, curve_id, field_id, field_inverse,
+               field_modulus, i32, i64, load, msm, msm_batch, msm_submit, multiplicative_generator, ntt, ntt_points_device, ptr, root_of_unity,
+               scalar_field, u32, u64, vec_op, vp)
 
 def best_multiexp(coeffs, bases):
     if int(coeffs.shape[0]) != bases.n:
@@ -321,53 +312,49 @@ class ExprOp(ctypes.Structure):
     _fields_ = [("op", ctypes.c_uint8), ("pad", ctypes.c_uint8), ("rot", ctypes.c_int16), ("arg", ctypes.c_uint32)]
 
 
-ZK_ERR_INVALID_ARG = -1        # include/zkcp_amd.h
 EXPR_CODES = {"col": 0, "const": 1, "add": 2, "sub": 3, "mul": 4, "neg": 5, "scale": 6}
 
-
-def _plib():
-    lib = load()
-    u64, vp, i32, u32 = ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32
-    pp = ctypes.POINTER(ctypes.c_void_p)
-    lib.zk_batch_invert_device.argtypes = [i32, vp, u64, vp]
-    lib.zk_prefix_product_device.argtypes = [i32, vp, vp, u64, vp, vp, vp]
-    lib.zk_halo2_permutation_product_device.argtypes = [i32, u32, pp, pp, u32, vp, vp, vp, u32, vp, vp, vp, vp]
-    lib.zk_halo2_lookup_product_device.argtypes = [i32, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]
-    lib.zk_halo2_permute_expression_pair_device.argtypes = [i32, vp, vp, u64, vp, vp, vp]
-    lib.zk_inner_product_device.argtypes = [i32, vp, vp, u64, vp, vp]
-    lib.zk_vec_fold_device.argtypes = [i32, vp, u64, vp, vp]
-    lib.zk_ipa_fold_bases_device.argtypes = [i32, vp, u64, vp, vp]
-    lib.zk_ipa_virtual_scalars_device.argtypes = [i32, vp, vp, u64, u64, vp, vp, vp]
-    lib.zk_ipa_update_weights_device.argtypes = [i32, vp, u64, u64, vp, vp]
-    lib.zk_ipa_collapse_device.argtypes = [i32, u64, vp, u64, u64, vp, vp]
-    lib.zk_ipa_collapse_range_device.argtypes = [i32, u64, vp, u64, u64, u64, u64, vp, vp]
-    lib.zk_bases_precompute_shifts.argtypes = [i32, u64]
-    lib.zk_bases_shift_tables.argtypes = [u64, ctypes.POINTER(u64)]
-    lib.zk_ipa_round_device.argtypes = [i32, u64, vp, vp, vp, u64, u64, vp, vp, vp, vp]
-    lib.zk_poly_eval_device.argtypes = [i32, vp, u64, vp, vp, vp]
-    lib.zk_vec_muladd_device.argtypes = [i32, vp, vp, u64, vp, vp]
-    lib.zk_vec_muladd_to_device.argtypes = [i32, vp, vp, vp, u64, vp, vp]
-    lib.zk_poly_eval_batch_device.argtypes = [i32, vp, u64, ctypes.c_uint32, u64, vp, vp, vp]
-    lib.zk_kate_division_device.argtypes = [i32, vp, vp, u64, vp, vp]
-    lib.zk_vec_powers_device.argtypes = [i32, vp, u64, vp, vp]
-    lib.zk_vec_fold_many_device.argtypes = [i32, vp, vp, ctypes.c_int64, u32, u64, vp, vp]
-    lib.zk_ipa_fold_round_device.argtypes = [i32, vp, vp, vp, u64, u64, vp, vp]
-    lib.zk_expr_eval_device.argtypes = [i32, ctypes.POINTER(ExprOp), u32, pp, u32, vp, u32, u32, u32, vp, vp]
-    lib.zk_expr_eval_lazy_device.argtypes = [i32, ctypes.POINTER(ExprOp), u32, pp, u32, vp, u32, u32, u32, vp, vp]
-    lib.zk_expr_configure.argtypes = [i32]
-    lib.zk_expr_specialised_source.argtypes = [i32, ctypes.POINTER(ExprOp), u32, u32, u32, ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
-    lib.zk_halo2_assembly_new.argtypes = [u64, u32, ctypes.POINTER(u64)]
-    lib.zk_halo2_assembly_copy.argtypes = [u64, vp, u64, ctypes.POINTER(u64)]
-    lib.zk_halo2_assembly_mapping.argtypes = [u64, vp]
-    lib.zk_halo2_assembly_free.argtypes = [u64]
-    lib.zk_halo2_permutation_sigmas_device.argtypes = [i32, u32, u32, vp, vp, vp, vp]
-    lib.zk_halo2_ipa_s_device.argtypes = [i32, u32, u32, vp, vp, vp, i32, vp]
-    lib.zk_halo2_ipa_compute_b.argtypes = [i32, u32, vp, vp, vp]
-    lib.zk_halo2_mock_eval_device.argtypes = [i32, u32, ctypes.POINTER(ExprOp), vp, u32, pp, vp, u32, vp, u32, vp, vp, vp]
-    lib.zk_halo2_mock_lookup_device.argtypes = [i32, u32, vp, vp, vp, vp, u64, vp, vp]
-    lib.zk_halo2_mock_permutation_device.argtypes = [i32, u32, u32, pp, vp, vp, vp, vp]
-    lib.zk_halo2_mock_failures_device.argtypes = [vp, u64, u64, vp, vp, vp, vp]
-    return lib
+pp = ptr(vp)
+SIGNATURES = {
+    "zk_batch_invert_device": [i32, vp, u64, vp],
+    "zk_prefix_product_device": [i32, vp, vp, u64, vp, vp, vp],
+    "zk_halo2_permutation_product_device": [i32, u32, pp, pp, u32, vp, vp, vp, u32, vp, vp, vp, vp],
+    "zk_halo2_lookup_product_device": [i32, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp],
+    "zk_halo2_permute_expression_pair_device": [i32, vp, vp, u64, vp, vp, vp],
+    "zk_inner_product_device": [i32, vp, vp, u64, vp, vp],
+    "zk_vec_fold_device": [i32, vp, u64, vp, vp],
+    "zk_ipa_fold_bases_device": [i32, vp, u64, vp, vp],
+    "zk_ipa_virtual_scalars_device": [i32, vp, vp, u64, u64, vp, vp, vp],
+    "zk_ipa_update_weights_device": [i32, vp, u64, u64, vp, vp],
+    "zk_ipa_collapse_device": [i32, u64, vp, u64, u64, vp, vp],
+    "zk_ipa_collapse_range_device": [i32, u64, vp, u64, u64, u64, u64, vp, vp],
+    "zk_ipa_round_device": [i32, u64, vp, vp, vp, u64, u64, vp, vp, vp, vp],
+    "zk_poly_eval_device": [i32, vp, u64, vp, vp, vp],
+    "zk_vec_muladd_device": [i32, vp, vp, u64, vp, vp],
+    "zk_vec_muladd_to_device": [i32, vp, vp, vp, u64, vp, vp],
+    "zk_poly_eval_batch_device": [i32, vp, u64, u32, u64, vp, vp, vp],
+    "zk_kate_division_device": [i32, vp, vp, u64, vp, vp],
+    "zk_vec_powers_device": [i32, vp, u64, vp, vp],
+    "zk_vec_fold_many_device": [i32, vp, vp, i64, u32, u64, vp, vp],
+    "zk_ipa_fold_round_device": [i32, vp, vp, vp, u64, u64, vp, vp],
+    "zk_expr_eval_device": [i32, ptr(ExprOp), u32, pp, u32, vp, u32, u32, u32, vp, vp],
+    "zk_expr_eval_lazy_device": [i32, ptr(ExprOp), u32, pp, u32, vp, u32, u32, u32, vp, vp],
+    "zk_expr_configure": [i32],
+    "zk_expr_specialised_source": [i32, ptr(ExprOp), u32, u32, u32, cp, u64, ptr(u64)],
+    "zk_halo2_assembly_new": [u64, u32, ptr(u64)],
+    "zk_halo2_assembly_copy": [u64, vp, u64, ptr(u64)],
+    "zk_halo2_assembly_mapping": [u64, vp],
+    "zk_halo2_assembly_free": [u64],
+    "zk_halo2_permutation_sigmas_device": [i32, u32, u32, vp, vp, vp, vp],
+    "zk_halo2_ipa_s_device": [i32, u32, u32, vp, vp, vp, i32, vp],
+    "zk_halo2_ipa_compute_b": [i32, u32, vp, vp, vp],
+    "zk_halo2_mock_eval_device": [i32, u32, ptr(ExprOp), vp, u32, pp, vp, u32, vp, u32, vp, vp, vp],
+    "zk_halo2_mock_lookup_device": [i32, u32, vp, vp, vp, vp, u64, vp, vp],
+    "zk_halo2_mock_permutation_device": [i32, u32, u32, pp, vp, vp, vp, vp],
+    "zk_halo2_mock_failures_device": [vp, u64, u64, vp, vp, vp, vp],
+}
+PROVER_EXPORTS = list(SIGNATURES)
+_plib = load        # the bound handle (tests and tools take it for raw calls)
 
 
 def _ptr_array(bufs):
@@ -418,9 +405,6 @@ def permute_expression_pair(field, inputs_mont, table_mont, usable_rows):
     return to_mont(a), to_mont(s_perm)
 
 
-ZK_ERR_LOOKUP = -9
-
-
 def permute_expression_pair_device(field, inputs, table, usable_rows, a_out=None, s_out=None, stream=0):
     """permute_expression_pair on device buffers (zk_halo2_permute_expression_pair_device): rows [0, usable_rows) of the
     Montgomery columns `inputs` and `table` in, (A', S') out -- rows [0, usable_rows) written, later rows left alone.  Outputs
@@ -443,7 +427,7 @@ def permute_expression_pair_device(field, inputs, table, usable_rows, a_out=None
 
 def batch_invert(field, a, stream=0):
     """arithmetic.rs BatchInvert on a device buffer, in place; zeros stay zero"""
-    _check(_plib().zk_batch_invert_device(field_id(field), _ptr(a), int(a.shape[0]), ctypes.c_void_p(stream)), "zk_batch_invert_device")
+    _call("zk_batch_invert_device", field_id(field), _ptr(a), int(a.shape[0]), ctypes.c_void_p(stream))
     return a
 
 
@@ -451,8 +435,8 @@ def prefix_product(field, a, out=None, first=None, want_total=False, stream=0):
     """out[i] = first * prod_{j<i} a[j] (in place when out is None) -> out, or (out, total)"""
     out = a if out is None else out
     tot = np.zeros(4, dtype=np.uint64)
-    _check(_plib().zk_prefix_product_device(field_id(field), _ptr(a), _ptr(out), int(a.shape[0]), _ptr(_np64(first)) if first is not None else None,
-                                            _ptr(tot) if want_total else None, ctypes.c_void_p(stream)), "zk_prefix_product_device")
+    _call("zk_prefix_product_device", field_id(field), _ptr(a), _ptr(out), int(a.shape[0]), _ptr(_np64(first)) if first is not None else None,
+          _ptr(tot) if want_total else None, ctypes.c_void_p(stream))
     return (out, tot) if want_total else out
 
 
@@ -462,10 +446,8 @@ def permutation_product(field, columns, sigmas, beta, gamma, delta, k, z_out, fi
     last = np.zeros(4, dtype=np.uint64)
     keep = [_np64(x) for x in (beta, gamma, delta)]
     zf = _np64(z_first) if z_first is not None else None
-    _check(_plib().zk_halo2_permutation_product_device(field_id(field), len(columns), _ptr_array(columns), _ptr_array(sigmas),
-                                                       first_column_index, _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), k,
-                                                       _ptr(zf) if zf is not None else None, _ptr(z_out), _ptr(last), ctypes.c_void_p(stream)),
-           "zk_halo2_permutation_product_device")
+    _call("zk_halo2_permutation_product_device", field_id(field), len(columns), _ptr_array(columns), _ptr_array(sigmas), first_column_index,
+          _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), k, _ptr(zf) if zf is not None else None, _ptr(z_out), _ptr(last), ctypes.c_void_p(stream))
     return last
 
 
@@ -473,15 +455,14 @@ def lookup_product(field, a, s, a_perm, s_perm, beta, gamma, z_out, stream=0):
     """plonk/lookup/prover.rs commit_product; returns Z after the last row (must be 1 for a valid lookup)"""
     last = np.zeros(4, dtype=np.uint64)
     keep = [_np64(beta), _np64(gamma)]
-    _check(_plib().zk_halo2_lookup_product_device(field_id(field), _ptr(a), _ptr(s), _ptr(a_perm), _ptr(s_perm), _ptr(keep[0]), _ptr(keep[1]),
-                                                  int(a.shape[0]), _ptr(z_out), _ptr(last), ctypes.c_void_p(stream)), "zk_halo2_lookup_product_device")
+    _call("zk_halo2_lookup_product_device", field_id(field), _ptr(a), _ptr(s), _ptr(a_perm), _ptr(s_perm), _ptr(keep[0]), _ptr(keep[1]),
+          int(a.shape[0]), _ptr(z_out), _ptr(last), ctypes.c_void_p(stream))
     return last
 
 
 def inner_product(field, a, b, stream=0):
     out = np.zeros(4, dtype=np.uint64)
-    _check(_plib().zk_inner_product_device(field_id(field), _ptr(a), _ptr(b), int(a.shape[0]), _ptr(out), ctypes.c_void_p(stream)),
-           "zk_inner_product_device")
+    _call("zk_inner_product_device", field_id(field), _ptr(a), _ptr(b), int(a.shape[0]), _ptr(out), ctypes.c_void_p(stream))
     return out
 
 
@@ -490,10 +471,9 @@ def vec_muladd(field, a, b, s, stream=0, out=None):
     and leave a alone (upstream clones the first polynomial of a fold)"""
     ss = _np64(s)
     if out is not None:
-        _check(_plib().zk_vec_muladd_to_device(field_id(field), _ptr(out), _ptr(a), _ptr(b), int(a.shape[0]), _ptr(ss), ctypes.c_void_p(stream)),
-               "zk_vec_muladd_to_device")
+        _call("zk_vec_muladd_to_device", field_id(field), _ptr(out), _ptr(a), _ptr(b), int(a.shape[0]), _ptr(ss), ctypes.c_void_p(stream))
         return out
-    _check(_plib().zk_vec_muladd_device(field_id(field), _ptr(a), _ptr(b), int(a.shape[0]), _ptr(ss), ctypes.c_void_p(stream)), "zk_vec_muladd_device")
+    _call("zk_vec_muladd_device", field_id(field), _ptr(a), _ptr(b), int(a.shape[0]), _ptr(ss), ctypes.c_void_p(stream))
     return a
 
 
@@ -501,8 +481,7 @@ def eval_polynomial(field, d_poly, x, stream=0):
     """arithmetic.rs eval_polynomial: p(x) for a device-resident coefficient vector; x, result: Montgomery limbs"""
     xx = _np64(x)
     out = np.zeros(4, dtype=np.uint64)
-    _check(_plib().zk_poly_eval_device(field_id(field), _ptr(d_poly), int(d_poly.shape[0]), _ptr(xx), _ptr(out), ctypes.c_void_p(stream)),
-           "zk_poly_eval_device")
+    _call("zk_poly_eval_device", field_id(field), _ptr(d_poly), int(d_poly.shape[0]), _ptr(xx), _ptr(out), ctypes.c_void_p(stream))
     return out
 
 
@@ -511,8 +490,7 @@ def eval_polynomials(field, d_polys, x, stream=0):
     xx = _np64(x)
     count, n = int(d_polys.shape[0]), int(d_polys.shape[1])
     out = np.zeros((count, 4), dtype=np.uint64)
-    _check(_plib().zk_poly_eval_batch_device(field_id(field), _ptr(d_polys), n, count, n, _ptr(xx), _ptr(out), ctypes.c_void_p(stream)),
-           "zk_poly_eval_batch_device")
+    _call("zk_poly_eval_batch_device", field_id(field), _ptr(d_polys), n, count, n, _ptr(xx), _ptr(out), ctypes.c_void_p(stream))
     return out
 
 
@@ -522,22 +500,21 @@ def vec_fold_many(field, out, polys, s, stream=0, reverse=False):
     ss = _np64(s)
     count, n = int(polys.shape[0]), int(polys.shape[1])
     first = polys[count - 1] if reverse else polys[0]
-    _check(_plib().zk_vec_fold_many_device(field_id(field), _ptr(out), _ptr(first), -n if reverse else n, count, n, _ptr(ss), ctypes.c_void_p(stream)),
-           "zk_vec_fold_many_device")
+    _call("zk_vec_fold_many_device", field_id(field), _ptr(out), _ptr(first), -n if reverse else n, count, n, _ptr(ss), ctypes.c_void_p(stream))
     return out
 
 
 def ipa_fold_round(field, p, b, half, u, w=None, m0=0, stream=0):
     """the three folds of one argument round in one launch (w: the fold-free form's weight vector over m0 generators)"""
     uu = _np64(u)
-    _check(_plib().zk_ipa_fold_round_device(field_id(field), _ptr(p), _ptr(b), _ptr(w) if w is not None else None, half, m0, _ptr(uu),
-                                            ctypes.c_void_p(stream)), "zk_ipa_fold_round_device")
+    _call("zk_ipa_fold_round_device", field_id(field), _ptr(p), _ptr(b), _ptr(w) if w is not None else None, half, m0, _ptr(uu),
+          ctypes.c_void_p(stream))
 
 
 def vec_powers(field, out, x, stream=0):
     """out[i] = x^i (the vector b of the inner-product argument: powers of x_3)"""
     xx = _np64(x)
-    _check(_plib().zk_vec_powers_device(field_id(field), _ptr(out), int(out.shape[0]), _ptr(xx), ctypes.c_void_p(stream)), "zk_vec_powers_device")
+    _call("zk_vec_powers_device", field_id(field), _ptr(out), int(out.shape[0]), _ptr(xx), ctypes.c_void_p(stream))
     return out
 
 
@@ -546,22 +523,21 @@ def kate_division(field, a, x, out=None, stream=0):
     and the multiopen prover resizes); in place unless `out` is given"""
     xx = _np64(x)
     out = a if out is None else out
-    _check(_plib().zk_kate_division_device(field_id(field), _ptr(a), _ptr(out), int(a.shape[0]), _ptr(xx), ctypes.c_void_p(stream)),
-           "zk_kate_division_device")
+    _call("zk_kate_division_device", field_id(field), _ptr(a), _ptr(out), int(a.shape[0]), _ptr(xx), ctypes.c_void_p(stream))
     return out
 
 
 def vec_fold(field, a, half, c, stream=0):
     """a[i] += c a[i + half] for i < half"""
     cc = _np64(c)
-    _check(_plib().zk_vec_fold_device(field_id(field), _ptr(a), half, _ptr(cc), ctypes.c_void_p(stream)), "zk_vec_fold_device")
+    _call("zk_vec_fold_device", field_id(field), _ptr(a), half, _ptr(cc), ctypes.c_void_p(stream))
     return a
 
 
 def ipa_fold_bases(curve, g, half, u, stream=0):
     """parallel_generator_collapse: g[i] <- affine(g[i] + [u] g[i + half]); g: device buffer [2 * half, 2 * limbs]"""
     uu = _np64(u)
-    _check(_plib().zk_ipa_fold_bases_device(curve_id(curve), _ptr(g), half, _ptr(uu), ctypes.c_void_p(stream)), "zk_ipa_fold_bases_device")
+    _call("zk_ipa_fold_bases_device", curve_id(curve), _ptr(g), half, _ptr(uu), ctypes.c_void_p(stream))
     return g
 
 
@@ -586,15 +562,14 @@ def evaluate_expression(field, program, columns, consts, log_n_ext, rot_scale, o
     29-bit limbs; constants and the output stay in the usual Montgomery form"""
     ops = _expr_ops(program)
     cs = _np64(consts).reshape(-1, 4) if len(consts) else np.zeros((1, 4), dtype=np.uint64)
-    fn = _plib().zk_expr_eval_lazy_device if lazy else _plib().zk_expr_eval_device
-    _check(fn(field_id(field), ops, len(program), _ptr_array(columns), len(columns), _ptr(cs), len(consts), log_n_ext,
-              rot_scale, _ptr(out), ctypes.c_void_p(stream)), "zk_expr_eval_lazy_device" if lazy else "zk_expr_eval_device")
+    _call("zk_expr_eval_lazy_device" if lazy else "zk_expr_eval_device", field_id(field), ops, len(program), _ptr_array(columns), len(columns),
+          _ptr(cs), len(consts), log_n_ext, rot_scale, _ptr(out), ctypes.c_void_p(stream))
     return out
 
 
 def expr_configure(jit="auto"):
     """zk_expr_configure: the lazy evaluator's specialised (hiprtc-compiled) kernel: "auto" (2^16 rows and more), "always", "never" """
-    _check(_plib().zk_expr_configure({"auto": 0, "always": 1, "never": 2}[jit]), "zk_expr_configure")
+    _call("zk_expr_configure", {"auto": 0, "always": 1, "never": 2}[jit])
 
 
 def expr_specialised_source(field, program, n_columns, n_consts):
@@ -709,11 +684,11 @@ class IpaProverVirtual:
             nl = _plib().zk_curve_base_limbs64(self.curve)
             lr = np.zeros((2, 3 * nl), dtype=np.uint64)
             v = np.zeros((2, 4), dtype=np.uint64)
-            _check(_plib().zk_ipa_round_device(self.curve, self.bases.handle, _ptr(self.p), _ptr(self.b), _ptr(self.W), self.m0, self.n,
-                                               _ptr(self.S), _ptr(lr), _ptr(v), ctypes.c_void_p(self.stream)), "zk_ipa_round_device")
+            _call("zk_ipa_round_device", self.curve, self.bases.handle, _ptr(self.p), _ptr(self.b), _ptr(self.W), self.m0, self.n, _ptr(self.S),
+                  _ptr(lr), _ptr(v), ctypes.c_void_p(self.stream))
             return lr[0], lr[1], v[0], v[1]
-        _check(_plib().zk_ipa_virtual_scalars_device(self.field, _ptr(self.p), _ptr(self.W), self.m0, self.n, _ptr(self.S[0]), _ptr(self.S[1]),
-                                                     ctypes.c_void_p(self.stream)), "zk_ipa_virtual_scalars_device")
+        _call("zk_ipa_virtual_scalars_device", self.field, _ptr(self.p), _ptr(self.W), self.m0, self.n, _ptr(self.S[0]), _ptr(self.S[1]),
+              ctypes.c_void_p(self.stream))
         L, R = zkdist.msm_batch_sharded(self.bases, self.S, montgomery=True, stream=self.stream)
         vl = inner_product(self.field, self.p[half:self.n], self.b[:half], stream=self.stream)
         vr = inner_product(self.field, self.p[:half], self.b[half:self.n], stream=self.stream)
@@ -742,8 +717,8 @@ class IpaProverVirtual:
             import torch
             share = self.n // world
             mine = g[rank * share:(rank + 1) * share]
-            _check(_plib().zk_ipa_collapse_range_device(self.curve, self.bases.handle, _ptr(self.W), self.m0, self.n, rank * share, share,
-                                                        _ptr(mine), ctypes.c_void_p(self.stream)), "zk_ipa_collapse_range_device")
+            _call("zk_ipa_collapse_range_device", self.curve, self.bases.handle, _ptr(self.W), self.m0, self.n, rank * share, share, _ptr(mine),
+                  ctypes.c_void_p(self.stream))
             # (the call above synchronises the stream: `mine` is complete)
             if isinstance(g, np.ndarray):                                   # the CPU test emulator: "device" memory is host memory
                 t = torch.from_numpy(np.ascontiguousarray(mine).view(np.int64))
@@ -764,8 +739,7 @@ class IpaProverVirtual:
                 g.copy_(torch.cat(outs).to(g.device))
                 torch.cuda.synchronize()
         else:
-            _check(_plib().zk_ipa_collapse_device(self.curve, self.bases.handle, _ptr(self.W), self.m0, self.n, _ptr(g), ctypes.c_void_p(self.stream)),
-                   "zk_ipa_collapse_device")
+            _call("zk_ipa_collapse_device", self.curve, self.bases.handle, _ptr(self.W), self.m0, self.n, _ptr(g), ctypes.c_void_p(self.stream))
         if self._own_bases is not None:
             self._own_bases.free()
         self._g = g                                   # adopted, not copied: kept alive here
@@ -814,7 +788,7 @@ class Assembly:
 
     def __init__(self, n, ncols):
         h = ctypes.c_uint64(0)
-        _check(_plib().zk_halo2_assembly_new(int(n), int(ncols), ctypes.byref(h)), "zk_halo2_assembly_new")
+        _call("zk_halo2_assembly_new", int(n), int(ncols), ctypes.byref(h))
         self.handle, self.n, self.ncols = h.value, int(n), int(ncols)
 
     def copy(self, left_column, left_row, right_column, right_row):
@@ -842,12 +816,12 @@ class Assembly:
     def mapping(self):
         """[ncols, n] uint64, mapping[c][r] = column << 32 | row of the cell (c, r) maps to"""
         out = np.zeros((self.ncols, self.n), dtype=np.uint64)
-        _check(_plib().zk_halo2_assembly_mapping(self.handle, _ptr(out)), "zk_halo2_assembly_mapping")
+        _call("zk_halo2_assembly_mapping", self.handle, _ptr(out))
         return out
 
     def free(self):
         if self.handle:
-            _check(_plib().zk_halo2_assembly_free(self.handle), "zk_halo2_assembly_free")
+            _call("zk_halo2_assembly_free", self.handle)
             self.handle = 0
 
 
@@ -862,8 +836,7 @@ def permutation_sigmas(field, k, mapping, sigmas=None, stream=0):
     d_map = _upload(mapping) if isinstance(mapping, np.ndarray) else mapping
     sigmas = _new_buffer((ncols, n, 4)) if sigmas is None else sigmas
     dl = delta(field)
-    _check(_plib().zk_halo2_permutation_sigmas_device(field_id(field), int(k), ncols, _ptr(d_map), _ptr(dl), _ptr(sigmas), ctypes.c_void_p(stream)),
-           "zk_halo2_permutation_sigmas_device")
+    _call("zk_halo2_permutation_sigmas_device", field_id(field), int(k), ncols, _ptr(d_map), _ptr(dl), _ptr(sigmas), ctypes.c_void_p(stream))
     return sigmas
 
 
@@ -1046,8 +1019,7 @@ def compute_s(field, u, init, out=None, accumulate=False, stream=0):
     elif int(out.shape[0]) != 1 << k:
         raise AssertionError("assertion failed: s.len() == 1 << k")
     uu, ii = _aligned16(uu), _aligned16(ii)
-    _check(_plib().zk_halo2_ipa_s_device(field_id(field), k, count, _ptr(uu), _ptr(ii), _ptr(out), int(bool(accumulate)), ctypes.c_void_p(stream)),
-           "zk_halo2_ipa_s_device")
+    _call("zk_halo2_ipa_s_device", field_id(field), k, count, _ptr(uu), _ptr(ii), _ptr(out), int(bool(accumulate)), ctypes.c_void_p(stream))
     return out
 
 
@@ -1055,7 +1027,7 @@ def compute_b(field, x, u):
     """verifier.rs compute_b(x, u) = prod_j (1 + u_j x^(2^(k-1-j))) on host limbs (zk_halo2_ipa_compute_b); u: [k, 4]"""
     uu, xx = _np64(u).reshape(-1, 4), _np64(x)
     out = np.zeros(4, dtype=np.uint64)
-    _check(_plib().zk_halo2_ipa_compute_b(field_id(field), int(uu.shape[0]), _ptr(xx), _ptr(uu), _ptr(out)), "zk_halo2_ipa_compute_b")
+    _call("zk_halo2_ipa_compute_b", field_id(field), int(uu.shape[0]), _ptr(xx), _ptr(uu), _ptr(out))
     return out
 
 
@@ -1350,9 +1322,8 @@ def mock_eval(field, k, programs, columns, poison_from, consts, status=None, val
         o = np.ascontiguousarray(offs[lo:hi + 1] - offs[lo]) if P else offs
         sub = ctypes.cast(ctypes.addressof(ops) + int(offs[lo]) * ctypes.sizeof(ExprOp), ctypes.POINTER(ExprOp))
         vout = None if values is None else ctypes.c_void_p(_ptr(values).value + lo * n * 32)
-        _check(_plib().zk_halo2_mock_eval_device(field_id(field), int(k), sub, _ptr(o), hi - lo, cols, _ptr(pf), len(columns), _ptr(cs), len(consts),
-                                                 vout, ctypes.c_void_p(_ptr(status).value + lo * n), ctypes.c_void_p(stream)),
-               "zk_halo2_mock_eval_device")
+        _call("zk_halo2_mock_eval_device", field_id(field), int(k), sub, _ptr(o), hi - lo, cols, _ptr(pf), len(columns), _ptr(cs), len(consts), vout,
+              ctypes.c_void_p(_ptr(status).value + lo * n), ctypes.c_void_p(stream))
     return status, values
 
 
@@ -1361,8 +1332,7 @@ def mock_failures(status, count, cap, stream=0):
     m = min(total, cap), ascending"""
     cap = int(min(cap, count))
     pos, kinds, total = np.zeros(max(cap, 1), dtype=np.uint64), np.zeros(max(cap, 1), dtype=np.uint8), ctypes.c_uint64(0)
-    _check(_plib().zk_halo2_mock_failures_device(_ptr(status), int(count), cap, _ptr(pos), _ptr(kinds), ctypes.byref(total), ctypes.c_void_p(stream)),
-           "zk_halo2_mock_failures_device")
+    _call("zk_halo2_mock_failures_device", _ptr(status), int(count), cap, _ptr(pos), _ptr(kinds), ctypes.byref(total), ctypes.c_void_p(stream))
     m = min(total.value, cap)
     return pos[:m], kinds[:m], total.value
 
@@ -1518,9 +1488,8 @@ class MockProver:
         for li, (ins, tab) in enumerate(self.lookups):
             a = first[li]
             if len(ins) == 1:
-                _check(_plib().zk_halo2_mock_lookup_device(self.field, self.k, _ptr(values[a]), ctypes.c_void_p(sbase + a * n), _ptr(values[a + 1]),
-                                                           ctypes.c_void_p(sbase + (a + 1) * n), u, ctypes.c_void_p(obase + li * n),
-                                                           ctypes.c_void_p(self.stream)), "zk_halo2_mock_lookup_device")
+                _call("zk_halo2_mock_lookup_device", self.field, self.k, _ptr(values[a]), ctypes.c_void_p(sbase + a * n), _ptr(values[a + 1]),
+                      ctypes.c_void_p(sbase + (a + 1) * n), u, ctypes.c_void_p(obase + li * n), ctypes.c_void_p(self.stream))
             else:                                        # HOST PATH: tuples of Python integers; Poison is its own component value
                 w = len(ins)
                 vals = _np64(_download(values[a:a + 2 * w]))[:, :u].astype(object)
@@ -1544,8 +1513,8 @@ class MockProver:
         idx, mapping = self.permutation
         status = _bytes_buffer(len(idx) * self.n)
         pf = np.ascontiguousarray(self.poison_from[idx], dtype=np.uint64)
-        _check(_plib().zk_halo2_mock_permutation_device(self.field, self.k, len(idx), _ptr_array([self.columns[c] for c in idx]), _ptr(pf), _ptr(mapping),
-                                                        _ptr(status), ctypes.c_void_p(self.stream)), "zk_halo2_mock_permutation_device")
+        _call("zk_halo2_mock_permutation_device", self.field, self.k, len(idx), _ptr_array([self.columns[c] for c in idx]), _ptr(pf), _ptr(mapping),
+              _ptr(status), ctypes.c_void_p(self.stream))
         pos, _, total = mock_failures(status, len(idx) * self.n, cap, self.stream)
         return [Permutation(idx[int(q) // self.n], int(q) % self.n) for q in pos.tolist()], total
 

@@ -12,31 +12,29 @@ import ctypes
 
 import numpy as np
 
-from . import ZkError, _check, _np64, _ptr, field_id, field_modulus, load
-
-PROVER_EXPORTS = ["zk_poseidon_create", "zk_poseidon_free", "zk_poseidon_permute_host", "zk_poseidon_hash_host", "zk_poseidon_permute_device",
-                  "zk_poseidon_hash_device", "zk_poseidon_merkle_tree_device", "zk_merkle_paths_device", "zk_vec_add_scalar_device"]
+from . import ZK_ERR_INVALID_ARG, ZkError, _call, _check, _np64, _ptr, field_id, field_modulus, i32, load, ptr, u32, u64, vp
 
 _MASK64 = (1 << 64) - 1
 
 
+SIGNATURES = {
+    "zk_poseidon_create": [i32, u32, u32, u32, u32, u32, u64, vp, vp, vp, ptr(u64)],
+    "zk_poseidon_free": [u64],
+    "zk_poseidon_permute_host": [u64, vp, u64],
+    "zk_poseidon_hash_host": [u64, vp, u32, u64, vp],
+    "zk_poseidon_permute_device": [u64, vp, u64, vp],
+    "zk_poseidon_hash_device": [u64, vp, u32, u64, vp, vp],
+    "zk_poseidon_merkle_tree_device": [u64, vp, u32, u32, vp, vp],
+    "zk_merkle_paths_device": [i32, vp, u32, vp, u64, vp, vp],
+    "zk_vec_add_scalar_device": [i32, vp, vp, u64, vp, vp],
+}
+PROVER_EXPORTS = list(SIGNATURES)
+_plib = load        # the bound handle (tests and tools take it for raw calls)
+
+
 def _bind(lib):
-    """the argument types of the nine entries on a loaded library"""
-    u64, vp, i32, u32 = ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32
-    lib.zk_poseidon_create.argtypes = [i32, u32, u32, u32, u32, u32, u64, vp, vp, vp, ctypes.POINTER(u64)]
-    lib.zk_poseidon_free.argtypes = [u64]
-    lib.zk_poseidon_permute_host.argtypes = [u64, vp, u64]
-    lib.zk_poseidon_hash_host.argtypes = [u64, vp, u32, u64, vp]
-    lib.zk_poseidon_permute_device.argtypes = [u64, vp, u64, vp]
-    lib.zk_poseidon_hash_device.argtypes = [u64, vp, u32, u64, vp, vp]
-    lib.zk_poseidon_merkle_tree_device.argtypes = [u64, vp, u32, u32, vp, vp]
-    lib.zk_merkle_paths_device.argtypes = [i32, vp, u32, vp, u64, vp, vp]
-    lib.zk_vec_add_scalar_device.argtypes = [i32, vp, vp, u64, vp, vp]
+    """kept for callers that hold a handle of load(): it is bound already"""
     return lib
-
-
-def _plib():
-    return _bind(load())
 
 
 def to_mont(p, values):
@@ -104,7 +102,7 @@ class PoseidonParameters:
         from .groth16 import _new_buffer
         total = int(np.prod(in_dev.shape[:-1]))
         if arity < 1 or total % arity:
-            raise ZkError(-1, "hash_batch: %d elements are no multiple of the arity %d" % (total, arity))
+            raise ZkError(ZK_ERR_INVALID_ARG, "hash_batch: %d elements are no multiple of the arity %d" % (total, arity))
         count = total // arity
         if out is None:
             out = _new_buffer((count, 4))
@@ -115,7 +113,7 @@ class PoseidonParameters:
         """zk_poseidon_permute_device: count states of `width` elements, in place"""
         total = int(np.prod(states_dev.shape[:-1]))
         if total % self.width:
-            raise ZkError(-1, "permute_batch: %d elements are no multiple of the width %d" % (total, self.width))
+            raise ZkError(ZK_ERR_INVALID_ARG, "permute_batch: %d elements are no multiple of the width %d" % (total, self.width))
         _check(self._lib.zk_poseidon_permute_device(self.handle, _ptr(states_dev), total // self.width, ctypes.c_void_p(stream)),
                "zk_poseidon_permute_device")
         return states_dev
@@ -251,7 +249,7 @@ class MerkleTree:
         n = total // leaf_arity if leaf_arity >= 1 else 0
         log_n = n.bit_length() - 1
         if n < 2 or n != 1 << log_n or n * leaf_arity != total:       # upstream: assert!(leaf_nodes_size > 1 && is_power_of_two)
-            raise ZkError(-1, "MerkleTree.new: %d leaf elements at leaf_arity %d are no power of two (> 1) of leaves" % (total, leaf_arity))
+            raise ZkError(ZK_ERR_INVALID_ARG, "MerkleTree.new: %d leaf elements at leaf_arity %d are no power of two (> 1) of leaves" % (total, leaf_arity))
         nodes = _new_buffer((2 * n - 1, 4))
         _check(params._lib.zk_poseidon_merkle_tree_device(params.handle, _ptr(leaves_dev), leaf_arity, log_n, _ptr(nodes), ctypes.c_void_p(stream)),
                "zk_poseidon_merkle_tree_device")
@@ -286,7 +284,7 @@ def elgamal_mask(field, m_dev, dh, out=None, stream=0):
     n = int(np.prod(m_dev.shape[:-1]))
     if out is None:
         out = _new_buffer(tuple(m_dev.shape))
-    _check(_plib().zk_vec_add_scalar_device(field_id(field), _ptr(out), _ptr(m_dev), n, _ptr(s), ctypes.c_void_p(stream)), "zk_vec_add_scalar_device")
+    _call("zk_vec_add_scalar_device", field_id(field), _ptr(out), _ptr(m_dev), n, _ptr(s), ctypes.c_void_p(stream))
     return out
 
 
